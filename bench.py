@@ -33,11 +33,22 @@ device path (one fused launch + completion wait) is reported beside it.
 torchrun's environment) before any GPU call; under torchrun WORLD_SIZE must
 equal --gpus.
 
-Each line carries the roofline (algorithmic flops or bytes
-of one eval / the measured step time, or / the dominant kernel's HIP-event
-launch time for the GLM; the GEMM family's executed flops beside it) and, on rank 0
-at N=1, the reference CPU path (oracle/_ref/ref_harness: the real Stan Math
-3.0.0 compiled from /root/reference) timed on one host core on a bounded sample.
+A plain run sets up, warms up, times --steps steps and prints one JSON line
+(metric, value, unit, ms_per_step, ...).  --dump-outputs DIR also writes what
+the last timed step returned to its caller as DIR/<name>.npy (float64); the
+inputs are the same in every run with the same arguments, so two builds can
+be compared output for output.
+
+--full adds everything else to the line: the parity guards against the
+reference's golden values before and after the timed steps, the roofline
+(algorithmic flops or bytes of one eval / the measured step
+time, or / the dominant kernel's HIP-event launch time for the GLM, from a
+profiled copy of the timed region; the GEMM family's executed flops beside
+it), each workload's further measurements (other argument types, the device
+path, the Eigen boundary's crossings), for the gp workload the config-4 GLM
+strong-scaling line (glm_strong) and, on rank 0 at N=1, the reference CPU
+path (oracle/_ref/ref_harness: the real Stan Math 3.0.0, where its sources
+were present at build time) timed on one host core on a bounded sample.
 """
 import argparse
 import ctypes
@@ -205,6 +216,9 @@ class GP(Workload):
 
     def units_per_step(self):
         return self.world  # one eval per replica
+
+    def outputs(self):
+        return {"fx": self.fx, "grad": self.g}
 
     def config(self):
         return {"workload": "gp_marginal_gradient", "N": self.N, "kernel": "exp_quad",
@@ -424,6 +438,9 @@ class GLM(Workload):
     def units_per_step(self):
         return 1  # one full-data gradient per step across all ranks
 
+    def outputs(self):
+        return {"fx": self.fx, "grad": self.g}
+
     def config(self):
         return {"workload": "bernoulli_logit_glm_gradient", "rows": self.R, "covariates": self.M,
                 "rows_per_rank": int(self.rows),
@@ -493,6 +510,14 @@ class MulChol(Workload):
     def units_per_step(self):
         return self.world
 
+    def outputs(self):
+        # the N^2 gradient stays in HBM (the caller receives a device buffer):
+        # fx of the last timed step, and [sum, L2 norm] of the gradient from
+        # one more evaluation of the same input (deterministic)
+        fx = self.fx.copy()
+        self.step(check=True)
+        return {"fx": fx, "grad_sum_l2": self.sl}
+
     def config(self):
         return {"workload": "multiply_cholesky_gradient", "N": self.N, "parallelism": f"replicas{self.world}",
                 "path": "stan::math::gradient (device-leaf) via header-only layer"}
@@ -542,6 +567,9 @@ class HVP(GP):
 
     def step(self):
         return self.bl.smg_bench_hvp_step(ptr(self.theta), ptr(self.v), ptr(self.fx), ptr(self.hv))
+
+    def outputs(self):
+        return {"fx": self.fx, "hv": self.hv}
 
     def guard(self):
         # no reference value at N=4096 (the reference's O(N^3) fvar tape is infeasible there);
@@ -636,6 +664,9 @@ class Normal(Workload):
 
     def units_per_step(self):
         return self.world
+
+    def outputs(self):
+        return {"fx": self.fx, "grad": self.g}
 
     def config(self):
         return {"workload": "normal_lpdf_gradient", "N": self.N, "parallelism": f"replicas{self.world}",
@@ -792,9 +823,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="gp")
     ap.add_argument("--rows", type=float, default=1e7, help="GLM rows (config 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity guards, the profiled copy of the timed region (roofline), each "
+                         "workload's further measurements, the CPU baseline and (gp) the glm_strong line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference CPU path")
     ap.add_argument("--no-glm-strong", action="store_true",
-                    help="gp workload: skip the config-4 GLM strong-scaling line (glm_strong)")
+                    help="with --full, gp workload: skip the config-4 GLM strong-scaling line (glm_strong)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -812,7 +848,7 @@ def main():
     from math_amd import hip
     from math_amd import srchash
     bl_path = os.path.join(ROOT, "math_amd", "lib", "libsmg_bench.so")
-    srchash.check(bl_path, "bench")  # (the GPU box cannot rebuild it: refuse a stale one)
+    srchash.check(bl_path, "bench")  # (built by build(), not here: refuse a stale one)
     bl = ctypes.CDLL(bl_path)
     bl.smg_bench_ctx.restype = ctypes.c_void_p
     bl.smg_bench_error.restype = ctypes.c_char_p
@@ -856,22 +892,18 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    ok, msg = wl.guard()  # parity guard on the measured configuration
-    if not ok:
-        raise SystemExit(f"parity failure: {msg}")
+    if args.full:
+        ok, msg = wl.guard()  # parity guard on the measured configuration
+        if not ok:
+            raise SystemExit(f"parity failure: {msg}")
 
     t = timed(args.steps)
     value = args.steps * wl.units_per_step() / t
     ms_per_step = 1e3 * t / args.steps
-    ok, msg = wl.guard()  # and on the last timed step
-    if not ok:
-        raise SystemExit(f"parity failure after the timed steps: {msg}")
-
-    # profiled copy of the timed region: HIP events on the context stream
-    lib.smg_profile_enable(ctx, 1)
-    tp = timed(args.steps)
-    fams = {f: hip.profile_read(lib, ctx, f) for f in hip.FAMILIES}
-    lib.smg_profile_enable(ctx, 0)
+    if args.dump_outputs and rank == 0:  # what the last timed step returned
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in wl.outputs().items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
 
     line = {
         "metric": wl.metric,
@@ -887,22 +919,33 @@ def main():
         "dtype": "f64",
         "data": wl.data,
         "config": wl.config(),
-        "roofline": wl.roofline(fams, args.steps, tp, ms_per_step),
     }
-    if hasattr(wl, "extra"):
-        line.update(wl.extra(timed, args.steps))
-    if getattr(wl, "parity", None):
-        line["parity"] = wl.parity
-    if getattr(wl, "reference_check", None):
-        line["reference_check"] = wl.reference_check
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            line["cpu_baseline"] = wl.cpu_baseline()
-        except Exception as e:  # noqa: BLE001
-            line["cpu_baseline"] = {"value": None, "error": str(e)[:200]}
-    strong = args.workload == "gp" and not args.no_glm_strong
-    if strong:
-        line["glm_strong"] = glm_strong(bl, args, rank, world, local, dist, timed, lib, ctx)
+    strong = args.full and args.workload == "gp" and not args.no_glm_strong
+    if args.full:
+        ok, msg = wl.guard()  # and on the last timed step
+        if not ok:
+            raise SystemExit(f"parity failure after the timed steps: {msg}")
+
+        # profiled copy of the timed region: HIP events on the context stream
+        lib.smg_profile_enable(ctx, 1)
+        tp = timed(args.steps)
+        fams = {f: hip.profile_read(lib, ctx, f) for f in hip.FAMILIES}
+        lib.smg_profile_enable(ctx, 0)
+
+        line["roofline"] = wl.roofline(fams, args.steps, tp, ms_per_step)
+        if hasattr(wl, "extra"):
+            line.update(wl.extra(timed, args.steps))
+        if getattr(wl, "parity", None):
+            line["parity"] = wl.parity
+        if getattr(wl, "reference_check", None):
+            line["reference_check"] = wl.reference_check
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                line["cpu_baseline"] = wl.cpu_baseline()
+            except Exception as e:  # noqa: BLE001
+                line["cpu_baseline"] = {"value": None, "error": str(e)[:200]}
+        if strong:
+            line["glm_strong"] = glm_strong(bl, args, rank, world, local, dist, timed, lib, ctx)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if (world > 1 and args.workload == "glm") or strong:

@@ -1,5 +1,5 @@
-"""Source hashes of the prebuilt binaries the GPU box runs but cannot rebuild
-(it has no /root/reference, so no Eigen / reference headers): the workload
+"""Source hashes of the binaries that build() leaves for the tests, smoke()
+and the benchmark to load without rebuilding: the workload
 library math_amd/lib/libsmg_bench.so, the C++ drop-in tests tests/cpp/_bin/*
 and the reference harness oracle/_ref/*.  Each is compiled with
 -DSMG_SOURCE_HASH=<this hash of its sources> (include/smg_source_tag.h keeps
@@ -21,6 +21,7 @@ _TAG = re.compile(rb"SMG_SOURCE_HASH=([0-9a-f]{16})")
 
 def _headers():
     h = sorted(glob.glob(os.path.join(ROOT, "math_amd", "include", "**", "*.hpp"), recursive=True))
+    h += sorted(glob.glob(os.path.join(ROOT, "third_party", "eigen_lite", "Eigen", "*")))
     return h + [os.path.join(ROOT, "include", "smg_hip.h")]
 
 

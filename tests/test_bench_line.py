@@ -1,5 +1,6 @@
-"""bench.py's contract on the GPU: the default (GP) line also carries the
-north star's strong-scaling config, the config-4 GLM at the same number of
+"""bench.py's contract on the GPU: a plain run prints the headline line alone
+and writes the last timed step's outputs on request; with --full the default
+(GP) line also carries the north star's strong-scaling config, the config-4 GLM at the same number of
 GPUs (glm_strong: 1e7 rows x 256 sharded over the ranks, one ncclAllReduce
 per gradient; at one GPU through a one-rank RCCL communicator, the path
 every rank of an 8-GPU run takes)."""
@@ -8,15 +9,42 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from _util import ROOT
+from _util import ROOT, golden, near_rel
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run: one JSON line with the headline's fields and none of the
+    --full measurements; --dump-outputs writes the last timed step's value and
+    gradient (float64), equal to the reference's golden gradient at 1e-10."""
+    out = str(tmp_path / "out")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", out], capture_output=True, text=True, timeout=120,
+                       cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["unit"] == "gradient evals/s" and "N=4096" in d["metric"]
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for k in ("roofline", "glm_strong", "cpu_baseline", "reference_input_types"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["fx.npy", "grad.npy"]
+    fx, g = np.load(os.path.join(out, "fx.npy")), np.load(os.path.join(out, "grad.npy"))
+    assert fx.dtype == np.float64 and g.dtype == np.float64 and fx.shape == (1,) and g.shape == (3,)
+    gd = golden("gp_N4096")
+    near_rel(fx, gd["fx"], 1e-12, what="fx")
+    near_rel(g, gd["grad"], 1e-10, what="grad")
 
 
 @pytest.mark.gpu
 def test_bench_default_line_carries_glm_strong():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240,
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240,
                        cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]

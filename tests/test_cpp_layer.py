@@ -89,6 +89,14 @@ def test_sweep_bridges_linear_in_tape_length():
     assert t4 < 8 * t1 + 2e-3, (t1, t4)
 
 
+def test_eigen_stand_in_host_semantics():
+    """third_party/eigen_lite (the Eigen the tree builds against where none is
+    installed; CPU, no device call): column-major storage, the row-by-row comma
+    initialiser, vector <-> matrix shape conversions, Map views, lower / upper
+    triangular solves, and balanced construction / destruction of elements."""
+    assert _run("test_eigen_lite", "").strip() == "ok"
+
+
 def test_cpp_programs_built():
     for name in ("test_gp_tape", "test_functors", "test_tape_cpu"):
         assert os.path.exists(os.path.join(BIN, name)), f"{name} not built (run __graft_entry__.build())"

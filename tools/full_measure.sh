@@ -8,7 +8,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
 for w in gp glm mulchol hvp; do
-  timeout -k 10 400 python bench.py --workload $w > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail $O/${TAG}_bench_$w.err; exit 1; }
+  timeout -k 10 400 python bench.py --workload $w --full > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail $O/${TAG}_bench_$w.err; exit 1; }
 done
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/${TAG}_prof.log 2>&1 || exit 1

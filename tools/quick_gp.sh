@@ -11,7 +11,7 @@ if [ -n "$K" ]; then
   tail -2 $O/${TAG}_pytest.log
 fi
 for w in ${WLS:-gp}; do
-  timeout -k 10 400 python bench.py --workload $w --steps 20 --no-cpu-baseline > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail $O/${TAG}_bench_$w.err; exit 1; }
+  timeout -k 10 400 python bench.py --workload $w --steps 20 --full --no-cpu-baseline > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err || { tail $O/${TAG}_bench_$w.err; exit 1; }
   python -c "import json;d=json.load(open('$O/${TAG}_bench_$w.json'));print('$w', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 done
 [ "${PROF:-1}" = 1 ] || exit 0
