@@ -209,6 +209,32 @@ int smg_gp_exp_quad_cov_nd_fwd(smg_ctx* ctx, const double* x, int D, int n, doub
 int smg_gp_exp_quad_cov_nd_rev(smg_ctx* ctx, const double* x, int D, int n, double sigma,
                                double l, const double* Kadj, int ldka, double* out2);
 
+/* The covariance family of the GP path.  With d = |x_i - x_j| (D == 1: the
+ * absolute difference, no square root; D > 1: sqrt of the squared distance
+ * summed in coordinate order) and K_ii = sigma^2:
+ *   SMG_GP_EXP_QUAD     K_ij = sigma^2 exp(-d^2 / (2 l^2))          (the entries above)
+ *   SMG_GP_EXPONENTIAL  K_ij = sigma^2 exp(-d / l)                  dK/dl = K d / l^2
+ *   SMG_GP_MATERN32     K_ij = sigma^2 (1 + a) exp(-a),              a = sqrt(3) d / l
+ *                                                                   dK/dl = sigma^2 a^2 exp(-a) / l
+ *   SMG_GP_MATERN52     K_ij = sigma^2 (1 + a + a^2 / 3) exp(-a),    a = sqrt(5) d / l
+ *                                                                   dK/dl = sigma^2 a^2 (1 + a) exp(-a) / (3 l)
+ * (gp_exponential_cov / gp_matern32_cov / gp_matern52_cov of Stan Math 3.0.0,
+ * prim/mat/fun/).  dK/dsigma = 2 K / sigma, the diagonal included; no
+ * derivative divides by d, so coincident points give K = sigma^2 and dK/dl = 0. */
+enum smg_gp_family { SMG_GP_EXP_QUAD = 0, SMG_GP_EXPONENTIAL = 1, SMG_GP_MATERN32 = 2, SMG_GP_MATERN52 = 3 };
+/* K (n x n full, exactly symmetric, ld ldk) of `family` for x D x n
+ * column-major (point i at x + i D; D <= 8192).  Argument checks and n == 0 as
+ * smg_gp_exp_quad_cov_nd_fwd, which is this entry with SMG_GP_EXP_QUAD; an
+ * unknown family is SMG_ERR_ARG. */
+int smg_gp_cov_fwd(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l,
+                   double* K, int ldk);
+/* out2[0] += d/dsigma = 2 (sum_{i != j} Kadj_ij K_ij + sigma^2 sum_i Kadj_ii) / sigma,
+ * out2[1] += d/dl     = sum_{i != j} Kadj_ij dK_ij/dl   (the family's dK/dl above)
+ * from the full adjoint Kadj (ld ldka); K is recomputed from x, fixed-order
+ * sums.  smg_gp_exp_quad_cov_nd_rev is this entry with SMG_GP_EXP_QUAD. */
+int smg_gp_cov_rev(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l,
+                   const double* Kadj, int ldka, double* out2);
+
 /* Tangent of the same covariance along (sigma', l') -- what the fvar<var>
  * instantiation of gp_exp_quad_cov computes inside hessian_times_vector
  * (mix/mat/functor/hessian_times_vector.hpp:13-40):
@@ -507,6 +533,17 @@ int smg_cholesky_inverse_adjoint(smg_ctx* ctx, const double* C, int ldc, int n, 
 int smg_gp_inverse_adjoint(smg_ctx* ctx, const double* C, int ldc, int n, const double* s, int k,
                            long long s_stride, double adj, const double* K0, int ldk, const double* x, int D,
                            double sigma, double l, double* dadj, double* out2);
+/* The same pass for K0 = the covariance of `family` (smg_gp_family;
+ * smg_gp_inverse_adjoint is SMG_GP_EXP_QUAD): dadj as above and
+ *   out2 = [2 sum_{i>=j} G_ij K0_ij / sigma, sum_{i>j} G_ij dK0_ij/dl],
+ * the l-derivative as K0_ij times a rational weight of a = c d_ij (no exp:
+ * K0 is read), scaled once in the final pass:
+ *   exponential a / l,  Matern 3/2 a^2 / ((1 + a) l),
+ *   Matern 5/2 a^2 (1 + a) / (3 l (1 + a + a^2 / 3)).
+ * Written (not accumulated); an unknown family is SMG_ERR_ARG. */
+int smg_gp_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
+                               long long s_stride, double adj, const double* K0, int ldk, const double* x, int D,
+                               double sigma, double l, double* dadj, double* out2);
 int smg_cholesky_mvn_rev_v(smg_ctx* ctx, int n, const double* s, int k, long long s_stride, double adj,
                            double* Aadj, int ldaa, double* ws, int c_formed);
 /* smg_cholesky_fwd_checked_mark that also queues the top half's part of

@@ -18,6 +18,7 @@
 // (stan/math/rev/fun/cholesky_decompose.hpp).
 #include "smg_internal.h"
 #include "tri_small.h"
+#include "gp_family.h"
 
 #include <vector>
 
@@ -162,12 +163,15 @@ __global__ void k_chol_mvn_adj(const double* __restrict__ C, int ldc, int n, con
 // K0_ij d2_ij] with g = Phi(sum_o s_o s_o^T - k C) (adj factored out).  A
 // workgroup takes the column pair (j, n - 1 - j) (balanced: n + 1 rows), its
 // threads the rows at or below the diagonal; PAIRS: two rows per thread with
-// 16-byte loads (even n, 16-byte aligned operands, D == 1).
-template <bool PAIRS>
+// 16-byte loads (even n, 16-byte aligned operands, D == 1).  F: the covariance
+// family (gp_family.h): the third partial is sum_{i>j} g_ij K0_ij w_ij with
+// its weight w (dK/dl = K0 w times the scale k_gp_inv_final applies; d2_ij for
+// exp_quad), cl its length-scale coefficient.
+template <int F, bool PAIRS>
 __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict__ C, int ldc, int n,
                                                       const double* __restrict__ s, int k, long long ss,
                                                       const double* __restrict__ K0, int ldk,
-                                                      const double* __restrict__ x, int D,
+                                                      const double* __restrict__ x, int D, double cl,
                                                       double* __restrict__ part) {
   __shared__ double lds[16];
   double sd = 0.0, sa = 0.0, sl = 0.0;
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
             const double d = xv.x - xj;
             const double t = g0 * kv.x;
             sa += t;
-            sl += t * (d * d);
+            sl += t * gp_fam<F>::w(gp_fam<F>::from_diff(d), cl);
           } else if (i == j) {
             sd += 0.5 * g0;
             sa += 0.5 * g0 * kv.x;
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
             const double d = xv.y - xj;
             const double t = g1 * kv.y;
             sa += t;
-            sl += t * (d * d);
+            sl += t * gp_fam<F>::w(gp_fam<F>::from_diff(d), cl);
           } else {  // i + 1 == j
             sd += 0.5 * g1;
             sa += 0.5 * g1 * kv.y;
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
             }
             const double t = g * kc[i];
             sa += t;
-            sl += t * d2;
+            sl += t * gp_fam<F>::w(gp_fam<F>::from_sq(d2), cl);
           }
         }
       }
@@ -252,7 +256,9 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
 
 // the fixed-order sum of k_gp_inv_reduce's partials: dadj = adj sum g_ii
 // (add_diag's d'), out2 = [2 adj sa / sigma, adj sl / l^3]
-// (rev/mat/fun/gp_exp_quad_cov.hpp:109-110)
+// (rev/mat/fun/gp_exp_quad_cov.hpp:109-110; the other families' scale of sl
+// is 1 / l or 1 / (3 l), gp_family.h)
+template <int F>
 __global__ void k_gp_inv_final(const double* __restrict__ part, int nparts, double adj, double sigma, double l,
                                double* dadj, double* out2) {
   __shared__ double lds[16];
@@ -271,7 +277,7 @@ __global__ void k_gp_inv_final(const double* __restrict__ part, int nparts, doub
     if (dadj) dadj[0] = adj * sd;
     if (out2) {
       out2[0] = adj * sa * 2 / sigma;
-      out2[1] = adj * sl / (l * l * l);
+      out2[1] = gp_fam<F>::lscale(adj * sl, l);
     }
   }
 }
@@ -343,6 +349,28 @@ int mvn_adj_epilogue(smg_ctx* ctx, const double* C, int n, const double* s, int 
   else
     hipLaunchKernelGGL(k_chol_mvn_adj, dim3(grid_for((long long)n * n)), dim3(256), 0, ctx->stream, C, n, n, s, k, ss,
                        adj, Aadj, ldaa);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// smg_gp_cov_inverse_adjoint for family F (checked arguments, n > 0)
+template <int F>
+int gp_inv_adjoint(smg_ctx* ctx, bool pairs, const double* C, int ldc, int n, const double* s, int k,
+                   long long s_stride, double adj, const double* K0, int ldk, const double* x, int D, double sigma,
+                   double l, double* dadj, double* out2) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const int half = (n + 1) / 2;
+  const int nb = half < 2048 ? half : 2048;
+  double* part = smg_ws(ctx, SMG_WS_RED, 3 * (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  const double cl = gp_fam<F>::coef(l);
+  if (pairs)
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, true>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0,
+                       ldk, x, D, cl, part);
+  else
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, false>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0,
+                       ldk, x, D, cl, part);
+  hipLaunchKernelGGL(k_gp_inv_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, adj, sigma, l, dadj, out2);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
 }
@@ -524,7 +552,15 @@ int smg_cholesky_inverse_adjoint(smg_ctx* ctx, const double* C, int ldc, int n, 
 int smg_gp_inverse_adjoint(smg_ctx* ctx, const double* C, int ldc, int n, const double* s, int k,
                            long long s_stride, double adj, const double* K0, int ldk, const double* x, int D,
                            double sigma, double l, double* dadj, double* out2) {
+  return smg_gp_cov_inverse_adjoint(ctx, SMG_GP_EXP_QUAD, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l,
+                                    dadj, out2);
+}
+
+int smg_gp_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
+                               long long s_stride, double adj, const double* K0, int ldk, const double* x, int D,
+                               double sigma, double l, double* dadj, double* out2) {
   if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
   if (n == 0) {
     if (dadj || out2) {
       const double z[2] = {0.0, 0.0};
@@ -539,23 +575,23 @@ int smg_gp_inverse_adjoint(smg_ctx* ctx, const double* C, int ldc, int n, const 
     if (!x) x = s, D = 1;
   }
   if (!C || !s || !K0 || !x || ldc < n || ldk < n || (out2 && !(sigma > 0 && l > 0))) return SMG_ERR_ARG;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const int half = (n + 1) / 2;
-  const int nb = half < 2048 ? half : 2048;
-  double* part = smg_ws(ctx, SMG_WS_RED, 3 * (size_t)nb);
-  if (!part) return SMG_ERR_OOM;
   const bool pairs = D == 1 && n % 2 == 0 && ldc % 2 == 0 && ldk % 2 == 0 && (k == 1 || s_stride % 2 == 0) &&
                      ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(s) |
                        reinterpret_cast<uintptr_t>(K0) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-  if (pairs)
-    hipLaunchKernelGGL(k_gp_inv_reduce<true>, dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0, ldk,
-                       x, D, part);
-  else
-    hipLaunchKernelGGL(k_gp_inv_reduce<false>, dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0,
-                       ldk, x, D, part);
-  hipLaunchKernelGGL(k_gp_inv_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, adj, sigma, l, dadj, out2);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL:
+      return gp_inv_adjoint<SMG_GP_EXPONENTIAL>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l,
+                                                dadj, out2);
+    case SMG_GP_MATERN32:
+      return gp_inv_adjoint<SMG_GP_MATERN32>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
+                                             out2);
+    case SMG_GP_MATERN52:
+      return gp_inv_adjoint<SMG_GP_MATERN52>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
+                                             out2);
+    default:
+      return gp_inv_adjoint<SMG_GP_EXP_QUAD>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
+                                             out2);
+  }
 }
 
 int smg_cholesky_inv_t_async(smg_ctx* ctx, const double* L, int ldl, const double* aux, int n, double* ws,

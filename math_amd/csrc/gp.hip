@@ -12,13 +12,20 @@
 // K_ij is recomputed from x instead of re-read (HBM: one read of Kadj).
 // Reductions are fixed-order (per-block partials + one ordered pass).
 //
+// The forward and reverse kernels are templated on the covariance family
+// (gp_family.h: exp_quad, exponential, Matern 3/2 and 5/2); their argument
+// inv_half_sq_l is the family's length-scale coefficient, 1 / (2 l^2) for
+// exp_quad.  The tangent kernels are exp_quad's alone.
+//
 // add_diag: prim/mat/fun/add_diag.hpp:20-55.
 #include "smg_internal.h"
+#include "gp_family.h"
 
 namespace {
 
 constexpr int GP_BLOCKS = 2048;
 
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_fwd(const double* __restrict__ x, int n, double s2,
                                                 double inv_half_sq_l, double* __restrict__ K,
                                                 int ldk) {
@@ -31,12 +38,13 @@ __global__ __launch_bounds__(256) void k_gp_fwd(const double* __restrict__ x, in
       v = s2;
     } else {
       const double d = (i > j) ? x[i] - xj : xj - x[i];
-      v = s2 * exp(-(d * d) * inv_half_sq_l);
+      v = gp_fam<F>::k(gp_fam<F>::from_diff(d), s2, inv_half_sq_l);
     }
     K[i + (size_t)j * ldk] = v;
   }
 }
 
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_rev_partials(const double* __restrict__ x, int n,
                                                          double s2, double inv_half_sq_l,
                                                          const double* __restrict__ Ka, int lda,
@@ -51,10 +59,7 @@ __global__ __launch_bounds__(256) void k_gp_rev_partials(const double* __restric
       as += a * s2;
     } else {
       const double d = (i > j) ? x[i] - x[j] : x[j] - x[i];
-      const double dist = d * d;
-      const double prod = a * (s2 * exp(-dist * inv_half_sq_l));
-      al += prod * dist;
-      as += prod;
+      gp_fam<F>::acc(a, gp_fam<F>::from_diff(d), s2, inv_half_sq_l, as, al);
     }
   }
   const double sl = block_sum(al, lds);
@@ -68,6 +73,7 @@ __global__ __launch_bounds__(256) void k_gp_rev_partials(const double* __restric
 
 // k_gp_rev_partials in the column form (16-byte reads of Kadj and x; a
 // workgroup walks whole columns); the same per-element terms, fixed order.
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_rev_partials_col2(const double* __restrict__ x, int n,
                                                               double s2, double inv_half_sq_l,
                                                               const double* __restrict__ Ka,
@@ -101,10 +107,7 @@ __global__ __launch_bounds__(256) void k_gp_rev_partials_col2(const double* __re
               as += av[h] * s2;
             } else {
               const double d = (i + h > j) ? xv[h] - xj : xj - xv[h];
-              const double dist = d * d;
-              const double prod = av[h] * (s2 * exp(-dist * inv_half_sq_l));
-              al += prod * dist;
-              as += prod;
+              gp_fam<F>::acc(av[h], gp_fam<F>::from_diff(d), s2, inv_half_sq_l, as, al);
             }
           }
         }
@@ -120,6 +123,7 @@ __global__ __launch_bounds__(256) void k_gp_rev_partials_col2(const double* __re
   }
 }
 
+template <int F>
 __global__ void k_gp_rev_final(const double* __restrict__ part, int nparts, double sigma, double l,
                                double* out2) {
   __shared__ double lds[16];
@@ -133,7 +137,7 @@ __global__ void k_gp_rev_final(const double* __restrict__ part, int nparts, doub
   sl = block_sum(sl, lds);
   if (threadIdx.x == 0) {
     out2[0] += ss * 2 / sigma;     // :110
-    out2[1] += sl / (l * l * l);   // :109
+    out2[1] += gp_fam<F>::lscale(sl, l);  // exp_quad: sl / l^3 (:109)
   }
 }
 
@@ -152,6 +156,7 @@ __global__ void k_add_diag_fwd(const double* __restrict__ A, int lda, int n, dou
 // even n and leading dimensions (the N=4096 GP): a workgroup walks whole
 // columns, each lane moves two rows with one 16-byte access, four accesses in
 // flight per lane.  Same per-element expressions as above (the same bits).
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_fwd_col2(const double* __restrict__ x, int n, double s2,
                                                      double inv_half_sq_l, double* __restrict__ K,
                                                      int ldk) {
@@ -172,13 +177,13 @@ __global__ __launch_bounds__(256) void k_gp_fwd_col2(const double* __restrict__ 
             v.x = s2;
           } else {
             const double d = (i > j) ? xi.x - xj : xj - xi.x;
-            v.x = s2 * exp(-(d * d) * inv_half_sq_l);
+            v.x = gp_fam<F>::k(gp_fam<F>::from_diff(d), s2, inv_half_sq_l);
           }
           if (i + 1 == j) {
             v.y = s2;
           } else {
             const double d = (i + 1 > j) ? xi.y - xj : xj - xi.y;
-            v.y = s2 * exp(-(d * d) * inv_half_sq_l);
+            v.y = gp_fam<F>::k(gp_fam<F>::from_diff(d), s2, inv_half_sq_l);
           }
           col[p] = v;
         }
@@ -360,6 +365,7 @@ __global__ void k_gp_tan_final(const double* __restrict__ part, int nparts, doub
 // column-major (point i at x + i D), d_ij^2 = squared_distance(x_i, x_j)
 // summed over the D coordinates in order.  A workgroup walks whole columns j;
 // x_j is staged in LDS, the row points are read from L2 (x is n D doubles).
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_nd_fwd(const double* __restrict__ x, int D, int n, double s2,
                                                    double inv_half_sq_l, double* __restrict__ K, int ldk) {
   extern __shared__ double xj[];
@@ -376,13 +382,14 @@ __global__ __launch_bounds__(256) void k_gp_nd_fwd(const double* __restrict__ x,
           const double t = xi[d] - xj[d];
           d2 += t * t;
         }
-        v = s2 * exp(-d2 * inv_half_sq_l);
+        v = gp_fam<F>::k(gp_fam<F>::from_sq(d2), s2, inv_half_sq_l);
       }
       K[i + (size_t)j * ldk] = v;
     }
   }
 }
 
+template <int F>
 __global__ __launch_bounds__(256) void k_gp_nd_rev_partials(const double* __restrict__ x, int D, int n, double s2,
                                                             double inv_half_sq_l, const double* __restrict__ Ka,
                                                             int lda, double* __restrict__ part) {
@@ -404,9 +411,7 @@ __global__ __launch_bounds__(256) void k_gp_nd_rev_partials(const double* __rest
           const double t = xi[d] - xj[d];
           d2 += t * t;
         }
-        const double prod = a * (s2 * exp(-d2 * inv_half_sq_l));
-        al += prod * d2;
-        as += prod;
+        gp_fam<F>::acc(a, gp_fam<F>::from_sq(d2), s2, inv_half_sq_l, as, al);
       }
     }
   }
@@ -426,6 +431,54 @@ inline int grid_for(long long tot) {
   return (int)g;
 }
 
+// K of family F for checked arguments, n > 0: the column form for aligned
+// scalar x, the 2-D grid otherwise, the LDS-staged form for D > 1.
+template <int F>
+int gp_fwd(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l, double* K, int ldk) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma;
+  const double c = gp_fam<F>::coef(l);
+  if (D > 1) {
+    hipLaunchKernelGGL(k_gp_nd_fwd<F>, dim3(n < 2048 ? n : 2048), dim3(256), D * sizeof(double), ctx->stream, x, D, n,
+                       s2, c, K, ldk);
+    SMG_LAUNCH_CHECK();
+    return SMG_OK;
+  }
+  if (col2_ok(x, 2, n) && col2_ok(K, ldk, n)) {
+    hipLaunchKernelGGL(k_gp_fwd_col2<F>, dim3(n < 2048 ? n : 2048), dim3(256), 0, ctx->stream, x, n, s2, c, K, ldk);
+    SMG_LAUNCH_CHECK();
+    return SMG_OK;
+  }
+  dim3 grid(smg_ceil_div(n, 256) > 16 ? 16 : smg_ceil_div(n, 256), n);
+  hipLaunchKernelGGL(k_gp_fwd<F>, grid, dim3(256), 0, ctx->stream, x, n, s2, c, K, ldk);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// out2 += [d/dsigma, d/dl] of family F from the full adjoint (same forms)
+template <int F>
+int gp_rev(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l, const double* Kadj, int ldka,
+           double* out2) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma;
+  const double c = gp_fam<F>::coef(l);
+  const bool col2 = D == 1 && col2_ok(x, 2, n) && col2_ok(Kadj, ldka, n);
+  int nb = (D > 1 || col2) ? n : grid_for((long long)n * n);
+  if (nb > GP_BLOCKS) nb = GP_BLOCKS;
+  double* part = smg_ws(ctx, SMG_WS_RED, 2 * (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  if (D > 1)
+    hipLaunchKernelGGL(k_gp_nd_rev_partials<F>, dim3(nb), dim3(256), D * sizeof(double), ctx->stream, x, D, n, s2, c,
+                       Kadj, ldka, part);
+  else if (col2)
+    hipLaunchKernelGGL(k_gp_rev_partials_col2<F>, dim3(nb), dim3(256), 0, ctx->stream, x, n, s2, c, Kadj, ldka, part);
+  else
+    hipLaunchKernelGGL(k_gp_rev_partials<F>, dim3(nb), dim3(256), 0, ctx->stream, x, n, s2, c, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_rev_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -434,70 +487,50 @@ int smg_gp_exp_quad_cov_fwd(smg_ctx* ctx, const double* x, int n, double sigma, 
                             double* K, int ldk) {
   if (!ctx || n < 0 || (n > 0 && (!x || !K || ldk < n))) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma;
-  const double ihl = 0.5 / (l * l);
-  if (col2_ok(x, 2, n) && col2_ok(K, ldk, n)) {
-    hipLaunchKernelGGL(k_gp_fwd_col2, dim3(n < 2048 ? n : 2048), dim3(256), 0, ctx->stream, x, n,
-                       s2, ihl, K, ldk);
-    SMG_LAUNCH_CHECK();
-    return SMG_OK;
-  }
-  dim3 grid(smg_ceil_div(n, 256) > 16 ? 16 : smg_ceil_div(n, 256), n);
-  hipLaunchKernelGGL(k_gp_fwd, grid, dim3(256), 0, ctx->stream, x, n, s2, ihl, K, ldk);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return gp_fwd<SMG_GP_EXP_QUAD>(ctx, x, 1, n, sigma, l, K, ldk);
 }
 
 int smg_gp_exp_quad_cov_rev(smg_ctx* ctx, const double* x, int n, double sigma, double l,
                             const double* Kadj, int ldka, double* out2) {
   if (!ctx || n < 0 || (n > 0 && (!x || !Kadj || !out2 || ldka < n))) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const long long tot = (long long)n * n;
-  const bool col2 = col2_ok(x, 2, n) && col2_ok(Kadj, ldka, n);
-  int nb = col2 ? n : grid_for(tot);
-  if (nb > GP_BLOCKS) nb = GP_BLOCKS;
-  double* part = smg_ws(ctx, SMG_WS_RED, 2 * (size_t)nb);
-  if (!part) return SMG_ERR_OOM;
-  if (col2) {
-    hipLaunchKernelGGL(k_gp_rev_partials_col2, dim3(nb), dim3(256), 0, ctx->stream, x, n,
-                       sigma * sigma, 0.5 / (l * l), Kadj, ldka, part);
-  } else {
-    hipLaunchKernelGGL(k_gp_rev_partials, dim3(nb), dim3(256), 0, ctx->stream, x, n, sigma * sigma,
-                       0.5 / (l * l), Kadj, ldka, part);
-  }
-  hipLaunchKernelGGL(k_gp_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return gp_rev<SMG_GP_EXP_QUAD>(ctx, x, 1, n, sigma, l, Kadj, ldka, out2);
 }
 
 int smg_gp_exp_quad_cov_nd_fwd(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l, double* K,
                                int ldk) {
-  if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !K || ldk < n))) return SMG_ERR_ARG;
-  if (n == 0) return SMG_OK;
-  if (D == 1) return smg_gp_exp_quad_cov_fwd(ctx, x, n, sigma, l, K, ldk);
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  hipLaunchKernelGGL(k_gp_nd_fwd, dim3(n < 2048 ? n : 2048), dim3(256), D * sizeof(double), ctx->stream, x, D, n,
-                     sigma * sigma, 0.5 / (l * l), K, ldk);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return smg_gp_cov_fwd(ctx, SMG_GP_EXP_QUAD, x, D, n, sigma, l, K, ldk);
 }
 
 int smg_gp_exp_quad_cov_nd_rev(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l,
                                const double* Kadj, int ldka, double* out2) {
-  if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !Kadj || !out2 || ldka < n))) return SMG_ERR_ARG;
+  return smg_gp_cov_rev(ctx, SMG_GP_EXP_QUAD, x, D, n, sigma, l, Kadj, ldka, out2);
+}
+
+int smg_gp_cov_fwd(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l, double* K,
+                   int ldk) {
+  if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !K || ldk < n))) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
-  if (D == 1) return smg_gp_exp_quad_cov_rev(ctx, x, n, sigma, l, Kadj, ldka, out2);
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const int nb = n < GP_BLOCKS ? n : GP_BLOCKS;
-  double* part = smg_ws(ctx, SMG_WS_RED, 2 * (size_t)nb);
-  if (!part) return SMG_ERR_OOM;
-  hipLaunchKernelGGL(k_gp_nd_rev_partials, dim3(nb), dim3(256), D * sizeof(double), ctx->stream, x, D, n,
-                     sigma * sigma, 0.5 / (l * l), Kadj, ldka, part);
-  hipLaunchKernelGGL(k_gp_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL: return gp_fwd<SMG_GP_EXPONENTIAL>(ctx, x, D, n, sigma, l, K, ldk);
+    case SMG_GP_MATERN32: return gp_fwd<SMG_GP_MATERN32>(ctx, x, D, n, sigma, l, K, ldk);
+    case SMG_GP_MATERN52: return gp_fwd<SMG_GP_MATERN52>(ctx, x, D, n, sigma, l, K, ldk);
+    default: return gp_fwd<SMG_GP_EXP_QUAD>(ctx, x, D, n, sigma, l, K, ldk);
+  }
+}
+
+int smg_gp_cov_rev(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l,
+                   const double* Kadj, int ldka, double* out2) {
+  if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !Kadj || !out2 || ldka < n))) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (n == 0) return SMG_OK;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL: return gp_rev<SMG_GP_EXPONENTIAL>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
+    case SMG_GP_MATERN32: return gp_rev<SMG_GP_MATERN32>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
+    case SMG_GP_MATERN52: return gp_rev<SMG_GP_MATERN52>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
+    default: return gp_rev<SMG_GP_EXP_QUAD>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
+  }
 }
 
 int smg_gp_exp_quad_cov_tangent_fwd(smg_ctx* ctx, const double* x, int n, double sigma, double l,

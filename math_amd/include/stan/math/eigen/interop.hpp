@@ -37,6 +37,7 @@
 #include <stan/math/rev/core.hpp>
 #include <stan/math/rev/fun/cholesky_decompose.hpp>
 #include <stan/math/rev/fun/gp_exp_quad_cov.hpp>
+#include <stan/math/rev/fun/gp_matern_cov.hpp>
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
@@ -845,6 +846,48 @@ inline dev_var_matrix gp_exp_quad_cov(const std::vector<Eigen::Matrix<double, R,
   return internal::gp_exp_quad_cov_dev(xd, D, sigma.val(), sigma.vi_, length_scale, nullptr, "magnitude",
                                        "length scale");
 }
+
+// ---- D-dimensional gp_exponential_cov / gp_matern32_cov / gp_matern52_cov
+namespace internal {
+/** The checks of rev/fun/gp_matern_cov.hpp in their order (x, magnitude,
+ * length scale), then the point sizes as squared_distance meets them. */
+template <typename T_x>
+inline dev_var_matrix gp_family_cov_points(int family, const char* fn, const std::vector<T_x>& x, double sigma,
+                                           vari* sigma_vi, double l, vari* l_vi) {
+  for (size_t i = 0; i < x.size(); ++i)
+    for (int d = 0; d < int(x[i].size()); ++d)
+      if (std::isnan(x[i](d))) gp_throw_x_nan(fn);
+  gp_check_hyper(fn, sigma, l);
+  int D = 1;
+  const dev_data<double> xd = gp_points_to_device(x, D);
+  return gp_family_cov_dev(family, fn, xd, D, sigma, sigma_vi, l, l_vi);
+}
+}  // namespace internal
+
+#define STAN_MATH_AMD_GP_FAMILY_POINT_OVERLOADS(FN, FAMILY)                                                     \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x, const var& sigma,             \
+                           const var& length_scale) {                                                          \
+    return internal::gp_family_cov_points(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale.val(),          \
+                                          length_scale.vi_);                                                   \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x, double sigma,                 \
+                           const var& length_scale) {                                                          \
+    return internal::gp_family_cov_points(FAMILY, #FN, x, sigma, nullptr, length_scale.val(),                  \
+                                          length_scale.vi_);                                                   \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x, const var& sigma,             \
+                           double length_scale) {                                                              \
+    return internal::gp_family_cov_points(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale, nullptr);      \
+  }
+
+STAN_MATH_AMD_GP_FAMILY_POINT_OVERLOADS(gp_exponential_cov, SMG_GP_EXPONENTIAL)
+STAN_MATH_AMD_GP_FAMILY_POINT_OVERLOADS(gp_matern32_cov, SMG_GP_MATERN32)
+STAN_MATH_AMD_GP_FAMILY_POINT_OVERLOADS(gp_matern52_cov, SMG_GP_MATERN52)
+
+#undef STAN_MATH_AMD_GP_FAMILY_POINT_OVERLOADS
 
 }  // namespace math
 }  // namespace stan

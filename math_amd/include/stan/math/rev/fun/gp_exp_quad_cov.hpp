@@ -30,8 +30,13 @@ inline void gp_check_positive(const char* fn, const char* name, double v) {
   }
 }
 
+// The node of every covariance family of the GP path (family_: smg_gp_family;
+// gp_exponential_cov / gp_matern32_cov / gp_matern52_cov in gp_matern_cov.hpp
+// build it with theirs): the families differ only in the C entries called.
 class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_sink {
  public:
+  const int family_;
+  const char* fn_;   // the function's name in error messages
   const double* x_;  // D x n column-major (point i at x_ + i D)
   const int n_;
   const int D_;
@@ -46,8 +51,11 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
   // it was deposited (dep_); exp_: consumed without forming K's dense adjoint
   inverse_adjoint dep_, exp_;
 
-  gp_exp_quad_cov_dev_vari(const double* x, int n, int D, double sigma, vari* sigma_vi, double l, vari* l_vi)
+  gp_exp_quad_cov_dev_vari(const double* x, int n, int D, double sigma, vari* sigma_vi, double l, vari* l_vi,
+                           int family = SMG_GP_EXP_QUAD, const char* fn = "gp_exp_quad_cov")
       : device_vari(0.0),
+        family_(family),
+        fn_(fn),
         x_(x),
         n_(n),
         D_(D),
@@ -59,7 +67,10 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
         out2_(amd::alloc_doubles(2)),
         pos_(ChainableStack::instance_->var_stack_.size() - 1) {
     K_->sink_ = this;
-    amd::check(smg_gp_exp_quad_cov_nd_fwd(amd::ctx(), x_, D_, n_, sigma_d_, l_d_, K_->val_, n_), "gp_exp_quad_cov");
+    amd::check(family_ == SMG_GP_EXP_QUAD
+                   ? smg_gp_exp_quad_cov_nd_fwd(amd::ctx(), x_, D_, n_, sigma_d_, l_d_, K_->val_, n_)
+                   : smg_gp_cov_fwd(amd::ctx(), family_, x_, D_, n_, sigma_d_, l_d_, K_->val_, n_),
+               fn_);
   }
 
   bool may_write_device_adjoint(const void*) const override { return false; }  // (host scalars only)
@@ -74,9 +85,13 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
   bool take_inverse_adjoint(const inverse_adjoint& d, double* dadj) override {
     if (d.n != n_) return false;
     if (dep_.C && dep_.sweep == ChainableStack::instance_->sweep_) return false;
-    amd::check(smg_gp_inverse_adjoint(amd::ctx(), d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->val_, n_, x_, D_, sigma_d_,
-                                      l_d_, dadj, (sigma_vi_ || l_vi_) ? out2_ : nullptr),
-               "gp_exp_quad_cov");
+    double* const out2 = (sigma_vi_ || l_vi_) ? out2_ : nullptr;
+    amd::check(family_ == SMG_GP_EXP_QUAD
+                   ? smg_gp_inverse_adjoint(amd::ctx(), d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->val_, n_, x_, D_,
+                                            sigma_d_, l_d_, dadj, out2)
+                   : smg_gp_cov_inverse_adjoint(amd::ctx(), family_, d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->val_, n_,
+                                                x_, D_, sigma_d_, l_d_, dadj, out2),
+               fn_);
     dep_ = d;
     return true;
   }
@@ -107,8 +122,11 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
     }
     if (!sigma_vi_ && !l_vi_) return;
     smg_ctx* c = amd::ctx();
-    amd::check(smg_memset(c, out2_, 0, 2 * sizeof(double)), "gp_exp_quad_cov");
-    amd::check(smg_gp_exp_quad_cov_nd_rev(c, x_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out2_), "gp_exp_quad_cov");
+    amd::check(smg_memset(c, out2_, 0, 2 * sizeof(double)), fn_);
+    amd::check(family_ == SMG_GP_EXP_QUAD
+                   ? smg_gp_exp_quad_cov_nd_rev(c, x_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out2_)
+                   : smg_gp_cov_rev(c, family_, x_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out2_),
+               fn_);
     if (sigma_vi_) add_pending_adjoint(sigma_vi_, out2_);
     if (l_vi_) add_pending_adjoint(l_vi_, out2_ + 1);
   }

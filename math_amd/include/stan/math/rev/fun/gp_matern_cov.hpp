@@ -1,0 +1,112 @@
+#ifndef STAN_MATH_REV_FUN_GP_MATERN_COV_HPP
+#define STAN_MATH_REV_FUN_GP_MATERN_COV_HPP
+
+// gp_exponential_cov, gp_matern32_cov and gp_matern52_cov (x, sigma,
+// length_scale) for scalar inputs x (the std::vector<Eigen vector> forms are
+// in eigen/interop.hpp), the Matern family of Stan Math 3.0.0
+// (prim/mat/fun/gp_exponential_cov.hpp, gp_matern32_cov.hpp,
+// gp_matern52_cov.hpp).  With d = |x_i - x_j|:
+//   gp_exponential_cov  K_ij = sigma^2 exp(-d / l)
+//   gp_matern32_cov     K_ij = sigma^2 (1 + a) exp(-a),             a = sqrt(3) d / l
+//   gp_matern52_cov     K_ij = sigma^2 (1 + a + a^2 / 3) exp(-a),   a = sqrt(5) d / l
+// The node is gp_exp_quad_cov's (rev/fun/gp_exp_quad_cov.hpp) with another
+// family: K on the device (smg_gp_cov_fwd), the GP marginal's inverse-form
+// adjoint through add_diag (smg_gp_cov_inverse_adjoint), the dense reverse
+// (smg_gp_cov_rev) when K has another consumer.
+//
+// Argument checks, in this order: every x entry is not NaN ("<fn>: x is nan,
+// but must not be nan!"), sigma is positive and finite under the name
+// "magnitude", length_scale under "length scale" ("... must be > 0!" /
+// "... must be finite!"), all std::domain_error.  This is the behaviour of
+// the reference's prim templates as recalled; the reference's sources are not
+// part of this repository and the messages could not be compared with them.
+// Not provided: a vector length scale (ARD), the cross-covariance (x1, x2)
+// overloads and the fvar<var> tangent.
+
+#include <stan/math/rev/fun/gp_exp_quad_cov.hpp>
+
+#include <cmath>
+#include <sstream>
+#include <stdexcept>
+#include <vector>
+
+namespace stan {
+namespace math {
+
+namespace internal {
+inline void gp_check_positive_finite(const char* fn, const char* name, double v) {
+  gp_check_positive(fn, name, v);
+  if (!std::isfinite(v)) {
+    std::ostringstream m;
+    m << fn << ": " << name << " is " << v << ", but must be finite!";
+    throw std::domain_error(m.str());
+  }
+}
+inline void gp_throw_x_nan(const char* fn) {
+  std::ostringstream m;
+  m << fn << ": x is nan, but must not be nan!";
+  throw std::domain_error(m.str());
+}
+inline void gp_check_x_not_nan(const char* fn, const std::vector<double>& x) {
+  for (size_t i = 0; i < x.size(); ++i)
+    if (std::isnan(x[i])) gp_throw_x_nan(fn);
+}
+inline void gp_check_hyper(const char* fn, double sigma, double l) {
+  gp_check_positive_finite(fn, "magnitude", sigma);
+  gp_check_positive_finite(fn, "length scale", l);
+}
+
+/** The node of `family` over checked arguments (x D x n on the device). */
+inline dev_var_matrix gp_family_cov_dev(int family, const char* fn, const dev_data<double>& x, int D, double sigma,
+                                        vari* sigma_vi, double l, vari* l_vi) {
+  const int n = D > 0 ? int(x.size() / size_t(D)) : 0;
+  auto* node = new gp_exp_quad_cov_dev_vari(x.data(), n, D, sigma, sigma_vi, l, l_vi, family, fn);
+  return dev_var_matrix(node->K_);
+}
+inline dev_var_matrix gp_family_cov(int family, const char* fn, const std::vector<double>& x, double sigma,
+                                    vari* sigma_vi, double l, vari* l_vi) {
+  gp_check_x_not_nan(fn, x);
+  gp_check_hyper(fn, sigma, l);
+  return gp_family_cov_dev(family, fn, to_dev_data(x), 1, sigma, sigma_vi, l, l_vi);
+}
+/** Device-resident x: its entries are the caller's to check. */
+inline dev_var_matrix gp_family_cov(int family, const char* fn, const dev_data<double>& x, double sigma,
+                                    vari* sigma_vi, double l, vari* l_vi) {
+  gp_check_hyper(fn, sigma, l);
+  return gp_family_cov_dev(family, fn, x, 1, sigma, sigma_vi, l, l_vi);
+}
+}  // namespace internal
+
+// (var, var), (double, var) and (var, double) for (sigma, length_scale), over
+// std::vector<double> x and device-resident x
+#define STAN_MATH_AMD_GP_FAMILY_OVERLOADS(FN, FAMILY)                                                       \
+  inline dev_var_matrix FN(const std::vector<double>& x, const var& sigma, const var& length_scale) {      \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale.val(),             \
+                                   length_scale.vi_);                                                      \
+  }                                                                                                        \
+  inline dev_var_matrix FN(const std::vector<double>& x, double sigma, const var& length_scale) {          \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma, nullptr, length_scale.val(), length_scale.vi_);  \
+  }                                                                                                        \
+  inline dev_var_matrix FN(const std::vector<double>& x, const var& sigma, double length_scale) {          \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale, nullptr);         \
+  }                                                                                                        \
+  inline dev_var_matrix FN(const dev_data<double>& x, const var& sigma, const var& length_scale) {         \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale.val(),             \
+                                   length_scale.vi_);                                                      \
+  }                                                                                                        \
+  inline dev_var_matrix FN(const dev_data<double>& x, double sigma, const var& length_scale) {             \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma, nullptr, length_scale.val(), length_scale.vi_);  \
+  }                                                                                                        \
+  inline dev_var_matrix FN(const dev_data<double>& x, const var& sigma, double length_scale) {             \
+    return internal::gp_family_cov(FAMILY, #FN, x, sigma.val(), sigma.vi_, length_scale, nullptr);         \
+  }
+
+STAN_MATH_AMD_GP_FAMILY_OVERLOADS(gp_exponential_cov, SMG_GP_EXPONENTIAL)
+STAN_MATH_AMD_GP_FAMILY_OVERLOADS(gp_matern32_cov, SMG_GP_MATERN32)
+STAN_MATH_AMD_GP_FAMILY_OVERLOADS(gp_matern52_cov, SMG_GP_MATERN52)
+
+#undef STAN_MATH_AMD_GP_FAMILY_OVERLOADS
+
+}  // namespace math
+}  // namespace stan
+#endif
