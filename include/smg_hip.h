@@ -601,6 +601,49 @@ int smg_cholesky_fwd_checked_mark_stream(smg_ctx* ctx, const double* A, int lda,
                                          double* aux, double* ws, int* started, double* packed, double* host_dst,
                                          int marker_base);
 
+/* The factorisation's input described instead of stored: A = K + d I with K
+ * the covariance of `family` for x (D x n column-major, as smg_gp_cov_fwd) --
+ * what cholesky_decompose(add_diag(gp_*_cov(x, sigma, l), d)) factors
+ * (rev/mat/fun/cholesky_decompose.hpp:378-387 on prim/mat/fun/add_diag.hpp:20-29's
+ * output).  sigma, l, d finite, sigma > 0, l > 0, 1 <= D <= 8192. */
+typedef struct smg_gp_source {
+  int family; /* smg_gp_family */
+  int D;
+  int n;
+  int pad_;
+  const double* x;
+  double sigma, l, d;
+} smg_gp_source;
+/* L (n x n, ld ldl, every element written) = the factorisation's input made
+ * from the description in ONE pass, no K and no K + d I in memory:
+ *   i > j  K_ij by smg_gp_cov_fwd's per-element expression (the same bits),
+ *   i == j sigma^2 + d (smg_add_diag_fwd's sum),   i < j  0.
+ * A generated K_ij that is NaN or infinite (from a non-finite x) latches
+ * SMG_ERR_NOT_SYMMETRIC, as check_symmetric's !(|a - a^T| <= 1e-8) does for
+ * such an element of a stored A (prim/mat/err/check_symmetric.hpp:45-46).
+ * 16-byte stores for D == 1, n % 64 == 0, even ldl and aligned x, L; any
+ * other shape by a generic form.  Columns are written in order. */
+int smg_gp_chol_source_fill(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl);
+/* smg_cholesky_fwd_checked_mark / _mark_inv / _mark_winv / _mark_stream with
+ * that pass in place of the checked copy of A (rev/mat/fun/cholesky_decompose.hpp:378-387:
+ * check_symmetric holds by construction except for the non-finite case
+ * above; not-positive-definite still comes from the panels).  Everything
+ * after the first kernel is the checked entry's. */
+int smg_cholesky_fwd_gp_mark(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* aux);
+int smg_cholesky_fwd_gp_mark_inv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* aux, double* ws,
+                                 int* started);
+int smg_cholesky_fwd_gp_mark_winv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* aux, double* ws,
+                                  int* started);
+int smg_cholesky_fwd_gp_mark_stream(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* aux,
+                                    double* ws, int* started, double* packed, double* host_dst, int marker_base);
+/* smg_gp_cov_inverse_adjoint without K0's values: K0_ij is recomputed from x
+ * with smg_gp_cov_fwd's per-element expression (sigma^2 on the diagonal), the
+ * sums and their order unchanged.  For a covariance node whose values were
+ * never formed (the generated factorisation above). */
+int smg_gp_cov_inverse_adjoint_x(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
+                                 long long s_stride, double adj, const double* x, int D, double sigma, double l,
+                                 double* dadj, double* out2);
+
 /* log_sum_exp(vector<var>) (rev/mat/fun/log_sum_exp.hpp:20-53):
  *   fwd: out = max + log(sum exp(x - max)); empty -> -inf; non-finite max -> max
  *   rev: xadj_i += adj * exp(x_i - lse)   (lse, adj: host values of the vari) */

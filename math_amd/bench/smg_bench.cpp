@@ -308,7 +308,7 @@ int smg_bench_bridge_cost(int n, int reps, double* out) {
       for (int touch = 0; touch < 2; ++touch) {
         start_nested();
         auto* node = new dev_matrix_vari(n, n);
-        amd::check(smg_fill_unif(amd::ctx(), node->val_, (long long)nn, SEED + 7, -1.0, 1.0, 1.0), "bridge");
+        amd::check(smg_fill_unif(amd::ctx(), node->raw_val(), (long long)nn, SEED + 7, -1.0, 1.0, 1.0), "bridge");
         dev_var_matrix A(node);
         var f0 = sum(A);  // a device consumer below the block (the sweep's common part)
         auto t0 = now();
@@ -333,7 +333,7 @@ int smg_bench_bridge_cost(int n, int reps, double* out) {
       }
       start_nested();  // a copy with one element replaced is not the block: gathered and uploaded
       auto* node = new dev_matrix_vari(n, n);
-      amd::check(smg_fill_unif(amd::ctx(), node->val_, (long long)nn, SEED + 7, -1.0, 1.0, 1.0), "bridge");
+      amd::check(smg_fill_unif(amd::ctx(), node->raw_val(), (long long)nn, SEED + 7, -1.0, 1.0, 1.0), "bridge");
       Eigen::Matrix<var, -1, -1> M2 = to_host_matrix(dev_var_matrix(node));
       M2(0, 0) = var(1.0);
       auto t3 = now();

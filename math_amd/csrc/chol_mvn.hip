@@ -166,12 +166,15 @@ __global__ void k_chol_mvn_adj(const double* __restrict__ C, int ldc, int n, con
 // 16-byte loads (even n, 16-byte aligned operands, D == 1).  F: the covariance
 // family (gp_family.h): the third partial is sum_{i>j} g_ij K0_ij w_ij with
 // its weight w (dK/dl = K0 w times the scale k_gp_inv_final applies; d2_ij for
-// exp_quad), cl its length-scale coefficient.
-template <int F, bool PAIRS>
+// exp_quad), cl its length-scale coefficient.  RECOMP: K0 is not read (null)
+// but recomputed from x with the forward's per-element expression
+// (gp_fam<F>::k; s2 = sigma^2 on the diagonal): the same values in the same
+// sums, without the n^2 / 2 doubles of K0's lower triangle.
+template <int F, bool PAIRS, bool RECOMP>
 __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict__ C, int ldc, int n,
                                                       const double* __restrict__ s, int k, long long ss,
                                                       const double* __restrict__ K0, int ldk,
-                                                      const double* __restrict__ x, int D, double cl,
+                                                      const double* __restrict__ x, int D, double cl, double s2,
                                                       double* __restrict__ part) {
   __shared__ double lds[16];
   double sd = 0.0, sa = 0.0, sl = 0.0;
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
       const int j = h == 0 ? b : n - 1 - b;
       if (h == 1 && j == b) break;
       const double* c = C + (size_t)j * ldc;
-      const double* kc = K0 + (size_t)j * ldk;
+      const double* kc = RECOMP ? nullptr : K0 + (size_t)j * ldk;
       if (PAIRS) {
         const double xj = x[j];
         double sjs[4];
@@ -190,7 +193,14 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
         const double2* k2 = reinterpret_cast<const double2*>(kc);
         const double2* x2 = reinterpret_cast<const double2*>(x);
         for (int p = (j >> 1) + threadIdx.x; p < (n >> 1); p += 256) {
-          const double2 cv = c2[p], kv = k2[p], xv = x2[p];
+          const double2 cv = c2[p], xv = x2[p];
+          double2 kv;
+          if (RECOMP) {  // (k_gp_fwd_col2's elements of rows 2p, 2p + 1; the row above the diagonal is unused)
+            kv.x = 2 * p == j ? s2 : gp_fam<F>::k(gp_fam<F>::from_diff(xv.x - xj), s2, cl);
+            kv.y = 2 * p + 1 == j ? s2 : gp_fam<F>::k(gp_fam<F>::from_diff(xv.y - xj), s2, cl);
+          } else {
+            kv = k2[p];
+          }
           double g0 = 0.0, g1 = 0.0;
           for (int o = 0; o < k; ++o) {
             const double2 sv = reinterpret_cast<const double2*>(s + o * ss)[p];
@@ -227,14 +237,18 @@ __global__ __launch_bounds__(256) void k_gp_inv_reduce(const double* __restrict_
           g -= k * c[i];
           if (i == j) {
             sd += 0.5 * g;
-            sa += 0.5 * g * kc[i];
+            sa += 0.5 * g * (RECOMP ? s2 : kc[i]);
           } else {
             double d2 = 0.0;
             for (int d = 0; d < D; ++d) {
               const double t = x[(size_t)i * D + d] - x[(size_t)j * D + d];
               d2 += t * t;
             }
-            const double t = g * kc[i];
+            // (the forward's element: k_gp_fwd from the difference for D == 1, k_gp_nd_fwd from d2)
+            const double k0 = !RECOMP  ? kc[i]
+                              : D == 1 ? gp_fam<F>::k(gp_fam<F>::from_diff(x[i] - x[j]), s2, cl)
+                                       : gp_fam<F>::k(gp_fam<F>::from_sq(d2), s2, cl);
+            const double t = g * k0;
             sa += t;
             sl += t * gp_fam<F>::w(gp_fam<F>::from_sq(d2), cl);
           }
@@ -364,12 +378,19 @@ int gp_inv_adjoint(smg_ctx* ctx, bool pairs, const double* C, int ldc, int n, co
   double* part = smg_ws(ctx, SMG_WS_RED, 3 * (size_t)nb);
   if (!part) return SMG_ERR_OOM;
   const double cl = gp_fam<F>::coef(l);
-  if (pairs)
-    hipLaunchKernelGGL((k_gp_inv_reduce<F, true>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0,
-                       ldk, x, D, cl, part);
+  const double s2 = sigma * sigma;
+  if (pairs && K0)
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, true, false>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k,
+                       s_stride, K0, ldk, x, D, cl, s2, part);
+  else if (K0)
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, false, false>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k,
+                       s_stride, K0, ldk, x, D, cl, s2, part);
+  else if (pairs)  // K0 recomputed from x (smg_gp_cov_inverse_adjoint_x)
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, true, true>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k,
+                       s_stride, K0, ldk, x, D, cl, s2, part);
   else
-    hipLaunchKernelGGL((k_gp_inv_reduce<F, false>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k, s_stride, K0,
-                       ldk, x, D, cl, part);
+    hipLaunchKernelGGL((k_gp_inv_reduce<F, false, true>), dim3(nb), dim3(256), 0, ctx->stream, C, ldc, n, s, k,
+                       s_stride, K0, ldk, x, D, cl, s2, part);
   hipLaunchKernelGGL(k_gp_inv_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, adj, sigma, l, dadj, out2);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
@@ -591,6 +612,35 @@ int smg_gp_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ld
     default:
       return gp_inv_adjoint<SMG_GP_EXP_QUAD>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
                                              out2);
+  }
+}
+
+int smg_gp_cov_inverse_adjoint_x(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
+                                 long long s_stride, double adj, const double* x, int D, double sigma, double l,
+                                 double* dadj, double* out2) {
+  // the diagonal sum alone needs no K0 at all, and n == 0 nothing
+  if (!out2 || n == 0)
+    return smg_gp_cov_inverse_adjoint(ctx, family, C, ldc, n, s, k, s_stride, adj, nullptr, ldc, x, D, sigma, l, dadj,
+                                      out2);
+  if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!C || !s || !x || ldc < n || !(sigma > 0 && l > 0)) return SMG_ERR_ARG;
+  const bool pairs = D == 1 && n % 2 == 0 && ldc % 2 == 0 && (k == 1 || s_stride % 2 == 0) &&
+                     ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(s) |
+                       reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL:
+      return gp_inv_adjoint<SMG_GP_EXPONENTIAL>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
+                                                dadj, out2);
+    case SMG_GP_MATERN32:
+      return gp_inv_adjoint<SMG_GP_MATERN32>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
+                                             dadj, out2);
+    case SMG_GP_MATERN52:
+      return gp_inv_adjoint<SMG_GP_MATERN52>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
+                                             dadj, out2);
+    default:
+      return gp_inv_adjoint<SMG_GP_EXP_QUAD>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
+                                             dadj, out2);
   }
 }
 

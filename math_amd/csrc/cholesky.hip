@@ -1630,7 +1630,7 @@ struct chol_stream_sink {
 };
 int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, double* Dinv,
              bool check_sym, bool mark = false, double* inv_ws = nullptr, int* inv_started = nullptr,
-             const chol_stream_sink* sink = nullptr, bool w_only = false);
+             const chol_stream_sink* sink = nullptr, bool w_only = false, const smg_gp_source* src = nullptr);
 
 }  // namespace
 
@@ -1696,6 +1696,27 @@ int smg_cholesky_fwd_checked_mark_winv(smg_ctx* ctx, const double* A, int lda, i
   return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true, true, ws, started, nullptr, true);
 }
 
+int smg_cholesky_fwd_gp_mark(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv) {
+  if (!src) return SMG_ERR_ARG;
+  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, nullptr, nullptr, nullptr, false, src);
+}
+
+int smg_cholesky_fwd_gp_mark_inv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv, double* ws,
+                                 int* started) {
+  if (!started || !src) return SMG_ERR_ARG;
+  *started = 0;
+  if (ws && !Dinv) return SMG_ERR_ARG;
+  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, nullptr, false, src);
+}
+
+int smg_cholesky_fwd_gp_mark_winv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv, double* ws,
+                                  int* started) {
+  if (!started || !src) return SMG_ERR_ARG;
+  *started = 0;
+  if (!ws || !Dinv) return SMG_ERR_ARG;
+  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, nullptr, true, src);
+}
+
 int smg_cholesky_inverse_wait(smg_ctx* ctx) {
   if (!ctx) return SMG_ERR_ARG;
   if (!ctx->inv_w_recorded) return SMG_ERR_ARG;
@@ -1724,6 +1745,22 @@ int smg_cholesky_fwd_checked_mark_stream(smg_ctx* ctx, const double* A, int lda,
   return rc;
 }
 
+int smg_cholesky_fwd_gp_mark_stream(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv,
+                                    double* ws, int* started, double* packed, double* host_dst, int marker_base) {
+  if (!started || !packed || !host_dst || marker_base < 0 || !src) return SMG_ERR_ARG;
+  *started = 0;
+  if (ws && !Dinv) return SMG_ERR_ARG;
+  if (marker_base + smg_cholesky_stream_panels(src->n) > 64) return SMG_ERR_ARG;
+  if (!ctx || smg_zero_stream_begin(ctx) != SMG_OK) return SMG_ERR_HIP;
+  const chol_stream_sink sink{packed, host_dst, marker_base};
+  const int rc = chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, &sink, false, src);
+  if (rc != SMG_OK) {  // (as smg_cholesky_fwd_checked_mark_stream: queued copies still target host_dst)
+    hipStreamSynchronize(ctx->zero_stream);
+    if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
+  }
+  return rc;
+}
+
 int smg_cholesky_stream_panel_cols(int n, int p, int* j0, int* j1) {
   const int np = smg_cholesky_stream_panels(n);
   if (!j0 || !j1 || p < 0 || p >= np) return SMG_ERR_ARG;
@@ -1739,8 +1776,10 @@ namespace {
 
 int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, double* Dinv,
              bool check_sym, bool mark, double* inv_ws, int* inv_started, const chol_stream_sink* sink,
-             bool w_only) {
-  if (!ctx || n < 0 || (n > 0 && (!A || !L || lda < n || ldl < n))) return SMG_ERR_ARG;
+             bool w_only, const smg_gp_source* src) {
+  // src: the input described (A unused): generated into L in place of the copy
+  if (src && (!ctx || !smg_gp_source_ok(src) || src->n != n || (n > 0 && (!L || ldl < n)))) return SMG_ERR_ARG;
+  if (!src && (!ctx || n < 0 || (n > 0 && (!A || !L || lda < n || ldl < n)))) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
   smg_prof_scope prof(ctx, SMG_FAM_CHOL_FWD);
   double* aux = Dinv;
@@ -1750,7 +1789,9 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
   }
   Dinv = aux;  // the SMG_NB level comes first
   const int tb = smg_ceil_div(n, 64);
-  if (A != L || lda != ldl) {
+  if (src) {
+    if (int e = smg_gp_chol_source_launch(ctx, src, L, ldl)) return e;
+  } else if (A != L || lda != ldl) {
     if (check_sym && n % 64 == 0 && lda % 2 == 0 && ldl % 2 == 0 &&
         ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(L)) & 15) == 0)
       hipLaunchKernelGGL(k_check_symmetric_copy2, dim3(tb * (tb + 1) / 2), dim3(256), 0,

@@ -479,9 +479,136 @@ int gp_rev(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l, 
   return SMG_OK;
 }
 
+// The factorisation's input generated in one pass (smg_gp_chol_source_fill):
+// L = tril(K + d I), zeros above, for K of family F -- what k_gp_fwd*,
+// k_add_diag_fwd* and the factorisation's checked copy left in L's buffer in
+// three passes.  A workgroup walks whole columns in order (the first panel's
+// land first), so a lane's stores of one instruction are contiguous.  The
+// strictly lower elements are k_gp_fwd* / k_gp_nd_fwd's expressions, the
+// diagonal k_add_diag_fwd*'s s2 + d (diag); a generated NaN / Inf is what the
+// copy's !(|a - a^T| <= 1e-8) flagged.
+//
+// Column form (D == 1, n % 64 == 0, 16-byte aligned x and columns): two rows
+// per 16-byte store, four stores in flight per lane; the pairs above the
+// diagonal's are zeros without a load of x.
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_chol_src_col2(const double* __restrict__ x, int n, double s2,
+                                                          double inv_half_sq_l, double diag,
+                                                          double* __restrict__ L, int ldl, int* status) {
+  const int np = n >> 1;
+  const double2* x2 = reinterpret_cast<const double2*>(x);
+  bool bad = false;
+  for (int j = blockIdx.x; j < n; j += gridDim.x) {
+    const double xj = x[j];
+    double2* col = reinterpret_cast<double2*>(L + (size_t)j * ldl);
+    const int pd = j >> 1;  // the pair holding the diagonal
+    for (int p0 = threadIdx.x; p0 < np; p0 += 4 * 256) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          double2 v = make_double2(0.0, 0.0);
+          if (p >= pd) {
+            const double2 xi = x2[p];
+            const int i = 2 * p;
+            if (i > j) {
+              v.x = gp_fam<F>::k(gp_fam<F>::from_diff(xi.x - xj), s2, inv_half_sq_l);
+              bad |= !(fabs(v.x - v.x) <= 1e-8);
+            } else if (i == j) {
+              v.x = diag;
+            }
+            if (i + 1 > j) {
+              v.y = gp_fam<F>::k(gp_fam<F>::from_diff(xi.y - xj), s2, inv_half_sq_l);
+              bad |= !(fabs(v.y - v.y) <= 1e-8);
+            } else {  // i + 1 == j
+              v.y = diag;
+            }
+          }
+          col[p] = v;
+        }
+      }
+    }
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, (int)SMG_ERR_NOT_SYMMETRIC);
+}
+
+// Generic form: any n, ldl and D (x_j staged in LDS as k_gp_nd_fwd does)
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_chol_src(const double* __restrict__ x, int D, int n, double s2,
+                                                     double inv_half_sq_l, double diag, double* __restrict__ L,
+                                                     int ldl, int* status) {
+  extern __shared__ double xj[];
+  bool bad = false;
+  for (int j = blockIdx.x; j < n; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x[(size_t)j * D + d];
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      double v = 0.0;
+      if (i == j) {
+        v = diag;
+      } else if (i > j) {
+        if (D == 1) {
+          v = gp_fam<F>::k(gp_fam<F>::from_diff(x[i] - xj[0]), s2, inv_half_sq_l);
+        } else {
+          const double* xi = x + (size_t)i * D;
+          double d2 = 0.0;
+          for (int d = 0; d < D; ++d) {
+            const double t = xi[d] - xj[d];
+            d2 += t * t;
+          }
+          v = gp_fam<F>::k(gp_fam<F>::from_sq(d2), s2, inv_half_sq_l);
+        }
+        bad |= !(fabs(v - v) <= 1e-8);
+      }
+      L[i + (size_t)j * ldl] = v;
+    }
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(status, (int)SMG_ERR_NOT_SYMMETRIC);
+}
+
+template <int F>
+int gp_chol_src(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl) {
+  const int n = s->n;
+  const double s2 = s->sigma * s->sigma;
+  const double c = gp_fam<F>::coef(s->l);
+  const double diag = s2 + s->d;
+  const int nb = n < 2048 ? n : 2048;
+  if (s->D == 1 && n % 64 == 0 && col2_ok(s->x, 2, n) && col2_ok(L, ldl, n))
+    hipLaunchKernelGGL(k_gp_chol_src_col2<F>, dim3(nb), dim3(256), 0, ctx->stream, s->x, n, s2, c, diag, L, ldl,
+                       ctx->status_d);
+  else
+    hipLaunchKernelGGL(k_gp_chol_src<F>, dim3(nb), dim3(256), s->D * sizeof(double), ctx->stream, s->x, s->D, n, s2, c,
+                       diag, L, ldl, ctx->status_d);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
 }  // namespace
 
+bool smg_gp_source_ok(const smg_gp_source* s) {
+  return s && s->n >= 0 && s->D >= 1 && s->D <= 8192 && s->family >= SMG_GP_EXP_QUAD && s->family <= SMG_GP_MATERN52 &&
+         (s->n == 0 || s->x) && s->sigma > 0 && s->l > 0 && std::isfinite(s->sigma) && std::isfinite(s->l) &&
+         std::isfinite(s->d);
+}
+
+// checked arguments (smg_gp_source_ok, n > 0, L n x n with ldl >= n)
+int smg_gp_chol_source_launch(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl) {
+  switch (s->family) {
+    case SMG_GP_EXPONENTIAL: return gp_chol_src<SMG_GP_EXPONENTIAL>(ctx, s, L, ldl);
+    case SMG_GP_MATERN32: return gp_chol_src<SMG_GP_MATERN32>(ctx, s, L, ldl);
+    case SMG_GP_MATERN52: return gp_chol_src<SMG_GP_MATERN52>(ctx, s, L, ldl);
+    default: return gp_chol_src<SMG_GP_EXP_QUAD>(ctx, s, L, ldl);
+  }
+}
+
 extern "C" {
+
+int smg_gp_chol_source_fill(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl) {
+  if (!ctx || !smg_gp_source_ok(src) || (src->n > 0 && (!L || ldl < src->n))) return SMG_ERR_ARG;
+  if (src->n == 0) return SMG_OK;
+  return smg_gp_chol_source_launch(ctx, src, L, ldl);
+}
 
 int smg_gp_exp_quad_cov_fwd(smg_ctx* ctx, const double* x, int n, double sigma, double l,
                             double* K, int ldk) {

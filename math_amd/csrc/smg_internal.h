@@ -191,6 +191,10 @@ double smg_inv_prog_cost(int n, int k, int part, bool inverses_here);
 // block inverses of the rows [row0, row0 + nrows) (multiples of 512), T: a
 // workspace (NULL: SMG_WS_TMP); Wout (ld n, may be NULL): the 512-level
 // block also written there when one launch forms it (*wrote)
+// a described GP input K + d I (smg_gp_source, gp.hip): its validity, and
+// tril of it generated into L (checked arguments, n > 0) on ctx->stream
+bool smg_gp_source_ok(const smg_gp_source* s);
+int smg_gp_chol_source_launch(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl);
 int smg_block_inverses_rows(smg_ctx* ctx, const double* L, int ldl, double* aux, int n, int row0, int nrows,
                             double* T, double* Wout = nullptr, bool* wrote = nullptr);
 // C = beta C (lower != 0: lower triangle only)

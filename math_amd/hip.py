@@ -113,6 +113,13 @@ _SIGS = {
     "smg_cholesky_stream_panel_cols": (_I, [_I, _I, _P, _P]),
     "smg_sum_strict_upper": (_I, [_P, _I, _P, _I, _P]),
     "smg_cholesky_fwd_checked_mark_stream": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I]),
+    # the factorisation's input described (smg_gp_source, passed by pointer) instead of stored
+    "smg_gp_chol_source_fill": (_I, [_P, _P, _P, _I]),
+    "smg_cholesky_fwd_gp_mark": (_I, [_P, _P, _P, _I, _P]),
+    "smg_cholesky_fwd_gp_mark_inv": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "smg_cholesky_fwd_gp_mark_winv": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "smg_cholesky_fwd_gp_mark_stream": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
+    "smg_gp_cov_inverse_adjoint_x": (_I, [_P, _I, _P, _I, _I, _P, _I, _L, _D, _P, _I, _D, _D, _P, _P]),
     "smg_log_sum_exp_fwd": (_I, [_P, _P, _L, _P]),
     "smg_log_sum_exp_rev": (_I, [_P, _P, _L, _D, _D, _P]),
     "smg_lgamma_fwd": (_I, [_P, _P, _L, _P]),

@@ -114,13 +114,56 @@ class structured_adjoint_sink {
    * ordered after its completion; null otherwise.  The consumer's forward
    * then takes the reference's products with inv_L instead of two solves. */
   virtual const double* inverse_factor() { return nullptr; }
+  /** A GP covariance node: what generates its output's values from x (family,
+   * x, D, n, sigma, l; d = 0).  False for any other node. */
+  virtual bool gp_source(smg_gp_source* out) {
+    (void)out;
+    return false;
+  }
+  /** An add_diag node whose output K + d I is still unformed and can be
+   * generated from x: the source a factorisation writes into its factor's
+   * buffer in place of the copy (smg_cholesky_fwd_gp_*).  False otherwise. */
+  virtual bool chol_source(smg_gp_source* out) {
+    (void)out;
+    return false;
+  }
 };
 
+class dev_matrix_vari;
+
+/** The producing node of a matrix whose values are deferred: it launches the
+ * forward kernels its constructor would have (dev_matrix_vari::val()). */
+class deferred_value_source {
+ public:
+  virtual void form_values(dev_matrix_vari* m) = 0;
+
+ protected:
+  ~deferred_value_source() = default;
+};
+
+namespace amd {
+/** Deferred values (dev_matrix_vari::defer_values) on this thread: off, every
+ * constructor launches its forward kernels eagerly (in-process A/B, tests). */
+inline bool& deferred_values_flag() {
+  static thread_local bool on = true;
+  return on;
+}
+inline bool deferred_values_enabled() { return deferred_values_flag(); }
+inline void set_deferred_values(bool on) { deferred_values_flag() = on; }
+/** How many deferred matrices had their values formed on this thread (tests). */
+inline size_t& materialisation_count() {
+  static thread_local size_t n = 0;
+  return n;
+}
+}  // namespace amd
+
 class dev_matrix_vari {
+  double* val_;  // device, column-major, ld = rows_ (allocated at construction; see val())
+  deferred_value_source* pending_ = nullptr;  // the producer still to form the values
+
  public:
   const int rows_;
   const int cols_;
-  double* val_;  // device, column-major, ld = rows_
   double* adj_;  // device, column-major, registered with the tape
   dev_structure structure_;
   double* aux_;  // node-specific device side data (e.g. Cholesky diagonal-block inverses)
@@ -131,9 +174,9 @@ class dev_matrix_vari {
   structured_adjoint_sink* sink_ = nullptr;
 
   dev_matrix_vari(int rows, int cols, dev_structure s = dev_structure::general)
-      : rows_(rows),
+      : val_(amd::alloc_doubles(size_t(rows) * cols)),
+        rows_(rows),
         cols_(cols),
-        val_(amd::alloc_doubles(size_t(rows) * cols)),
         adj_(amd::alloc_doubles(size_t(rows) * cols)),
         structure_(s),
         aux_(nullptr) {
@@ -141,6 +184,27 @@ class dev_matrix_vari {
   }
 
   size_t size() const { return size_t(rows_) * cols_; }
+
+  /** The values, for every reader: a deferred matrix's are formed first, by
+   * the kernels its producer's constructor would have launched (the same
+   * bits).  The pointer itself never changes. */
+  const double* val() {
+    if (pending_) force_values();
+    return val_;
+  }
+  /** The buffer without forming anything: for the producing node alone (its
+   * forward writes it, its reverse reads what that forward wrote). */
+  double* raw_val() { return val_; }
+  bool values_pending() const { return pending_ != nullptr; }
+  /** By the producing node, in place of its forward kernels. */
+  void defer_values(deferred_value_source* producer) { pending_ = producer; }
+  void force_values() {
+    deferred_value_source* p = pending_;
+    if (!p) return;
+    pending_ = nullptr;
+    ++amd::materialisation_count();
+    p->form_values(this);
+  }
 
   static inline void* operator new(size_t nbytes) {
     return ChainableStack::instance_->memalloc_.alloc(nbytes);
@@ -158,13 +222,13 @@ class dev_var_matrix {
   int rows() const { return vi_->rows_; }
   int cols() const { return vi_->cols_; }
   size_t size() const { return vi_->size(); }
-  const double* val_ptr() const { return vi_->val_; }
+  const double* val_ptr() const { return vi_->val(); }
   double* adj_ptr() const { return vi_->adj_; }
 
   /** Column-major host copy of the values (synchronising). */
   std::vector<double> val() const {
     std::vector<double> h(size());
-    amd::to_host(h.data(), vi_->val_, size());
+    amd::to_host(h.data(), vi_->val(), size());
     return h;
   }
   /** Column-major host copy of the adjoints (synchronising). */
@@ -218,7 +282,7 @@ struct dev_operand {
   dev_matrix_vari* vi = nullptr;  // null for data
   const double* data = nullptr;
   int rows = 0, cols = 0;
-  const double* val() const { return vi ? vi->val_ : data; }
+  const double* val() const { return vi ? vi->val() : data; }
   double* adj() const { return vi ? vi->adj_ : nullptr; }
   size_t size() const { return size_t(rows) * size_t(cols); }
 };
@@ -230,7 +294,7 @@ inline dev_operand operand(const dev_data<double>& d) { return dev_operand{nullp
  * its adjoint is read back by the caller, like x_var in gradient()). */
 inline dev_var_matrix to_dev_var_matrix(const double* host_colmajor, int rows, int cols) {
   auto* vi = new dev_matrix_vari(rows, cols);
-  amd::to_device(vi->val_, host_colmajor, size_t(rows) * cols);
+  amd::to_device(vi->raw_val(), host_colmajor, size_t(rows) * cols);
   return dev_var_matrix(vi);
 }
 
@@ -552,10 +616,10 @@ inline size_t materialise(dev_matrix_vari* m, const std::function<void(const hos
   b.n = b.layout == layout_dense ? m->size() : tril_count(size_t(m->rows_));
   b.first = static_cast<vari*>(st->memalloc_.alloc((b.n ? b.n : 1) * sizeof(vari)));
   b.dummy = b.layout == layout_lower ? new vari(0.0, vari::unstacked_tag{}) : nullptr;
-  const double* src = m->val_;
+  const double* src = m->val();
   if (b.layout != layout_dense && b.n) {
     double* t = amd::alloc_doubles(b.n);
-    amd::check(smg_pack_tril(amd::ctx(), 0, b.rows, m->val_, b.rows, t), "to_host");
+    amd::check(smg_pack_tril(amd::ctx(), 0, b.rows, m->val(), b.rows, t), "to_host");
     src = t;
   }
   stream_varis(b.first, src, b.n, [&] {
@@ -587,7 +651,7 @@ inline size_t materialise_diag(dev_matrix_vari* B, long base, vari* const* base_
   b.dummy = nullptr;
   if (b.n) {
     double* t = amd::alloc_doubles(b.n);
-    amd::check(smg_pack_tril(amd::ctx(), 2, int(b.n), B->val_, b.rows, t), "add_diag");
+    amd::check(smg_pack_tril(amd::ctx(), 2, int(b.n), B->val(), b.rows, t), "add_diag");
     stream_varis(b.first, t, b.n, nullptr);
   }
   return push_block(b);
@@ -663,7 +727,7 @@ inline dev_var_matrix to_dev_vars(const var* d, size_t n, int rows, int cols, co
       smg_ctx* c = amd::ctx();
       double* flag = amd::alloc_doubles(1);
       amd::check(smg_memset(c, flag, 0, sizeof(double)), nan_fn);
-      amd::check(smg_check_domain(c, node->val_, (long long)n, 0, flag), nan_fn);
+      amd::check(smg_check_domain(c, node->val(), (long long)n, 0, flag), nan_fn);
       double f = 0;
       amd::to_host(&f, flag, 1);
       if (f != 0.0)
@@ -687,7 +751,7 @@ inline dev_var_matrix to_dev_vars(const var* d, size_t n, int rows, int cols, co
       if (std::isnan(stage[i])) throw_not_nan(nan_fn, nan_name, i);
   auto* node = new dev_matrix_vari(rows, cols);
   if (n) {
-    amd::check(smg_memcpy_h2d(c, node->val_, stage, n * sizeof(double)), "to_dev");
+    amd::check(smg_memcpy_h2d(c, node->raw_val(), stage, n * sizeof(double)), "to_dev");
     amd::check(smg_sync(c), "to_dev");
   }
   new host_to_dev_vari(node, elems);

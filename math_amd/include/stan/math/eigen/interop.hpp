@@ -137,7 +137,7 @@ inline eig_in prepare(const Eigen::Matrix<var, R, C, O, MR, MC>& m, const char* 
       smg_ctx* c = amd::ctx();
       double* flag = amd::alloc_doubles(1);
       amd::check(smg_memset(c, flag, 0, sizeof(double)), nan_fn);
-      amd::check(smg_check_domain(c, e.node->val_, (long long)e.n, 0, flag), nan_fn);
+      amd::check(smg_check_domain(c, e.node->val(), (long long)e.n, 0, flag), nan_fn);
       double f = 0;
       amd::to_host(&f, flag, 1);
       if (f == 0.0) return e;
@@ -669,7 +669,7 @@ inline mvt_dev<var> mvt_to_dev(const std::vector<const var*>& p, int n) {
   }
   mvt_dev<var> out;
   for (size_t i = 0; i < p.size(); ++i) {
-    out.val.push_back(node->val_ + i * size_t(n));
+    out.val.push_back(node->val() + i * size_t(n));
     out.adj.push_back(node->adj_ + i * size_t(n));
   }
   return out;

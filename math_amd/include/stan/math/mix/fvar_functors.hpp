@@ -86,12 +86,12 @@ class multiply_lower_dev_vari : public device_vari {
   multiply_lower_dev_vari(dev_matrix_vari* A, dev_matrix_vari* B)
       : device_vari(0.0), A_(A), B_(B), C_(new dev_matrix_vari(A->rows_, B->cols_, dev_structure::lower)) {
     const int n = A->rows_;
-    amd::check(smg_multiply_lower_fwd(amd::ctx(), A_->val_, n, B_->val_, n, n, C_->val_, n), "multiply");
+    amd::check(smg_multiply_lower_fwd(amd::ctx(), A_->val(), n, B_->val(), n, n, C_->raw_val(), n), "multiply");
   }
   void chain() override {
     const int n = A_->rows_;
     double* ws = amd::alloc_doubles(size_t(n) * n);
-    amd::check(smg_multiply_lower_rev(amd::ctx(), A_->val_, n, B_->val_, n, C_->adj_, n, n, A_->adj_, n,
+    amd::check(smg_multiply_lower_rev(amd::ctx(), A_->val(), n, B_->val(), n, C_->adj_, n, n, A_->adj_, n,
                                       B_->adj_, n, ws),
                "multiply");
   }
@@ -108,8 +108,8 @@ class add_dev_vari : public device_vari {
   add_dev_vari(dev_matrix_vari* A, dev_matrix_vari* B)
       : device_vari(0.0), A_(A), B_(B), C_(new dev_matrix_vari(A->rows_, A->cols_)) {
     smg_ctx* c = amd::ctx();
-    amd::check(smg_copy_matrix(c, A->rows_, A->cols_, A->val_, A->rows_, C_->val_, C_->rows_, 0, 0), "add");
-    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, B->val_, 1, C_->val_, 1), "add");
+    amd::check(smg_copy_matrix(c, A->rows_, A->cols_, A->val(), A->rows_, C_->raw_val(), C_->rows_, 0, 0), "add");
+    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, B->val(), 1, C_->raw_val(), 1), "add");
   }
   void chain() override {
     smg_ctx* c = amd::ctx();
@@ -126,8 +126,8 @@ class tril_dev_vari : public device_vari {
   explicit tril_dev_vari(dev_matrix_vari* A)
       : device_vari(0.0), A_(A), C_(new dev_matrix_vari(A->rows_, A->cols_, dev_structure::lower)) {
     smg_ctx* c = amd::ctx();
-    amd::zero(C_->val_, C_->size());
-    amd::check(smg_add_tril(c, A->rows_, A->cols_, 1.0, A->val_, A->rows_, C_->val_, C_->rows_), "tril");
+    amd::zero(C_->raw_val(), C_->size());
+    amd::check(smg_add_tril(c, A->rows_, A->cols_, 1.0, A->val(), A->rows_, C_->raw_val(), C_->rows_), "tril");
   }
   void chain() override {
     amd::check(smg_add_tril(amd::ctx(), A_->rows_, A_->cols_, 1.0, C_->adj_, C_->rows_, A_->adj_, A_->rows_),
@@ -144,7 +144,7 @@ class lse_tangent_dev_vari : public device_vari {
   lse_tangent_dev_vari(double t, double lse, dev_matrix_vari* x, dev_matrix_vari* xd)
       : device_vari(t), x_(x), xd_(xd), lse_(lse) {}
   void chain() override {
-    amd::check(smg_lse_tangent_rev(amd::ctx(), x_->val_, xd_->val_, (long long)x_->size(), lse_, val_, adj_,
+    amd::check(smg_lse_tangent_rev(amd::ctx(), x_->val(), xd_->val(), (long long)x_->size(), lse_, val_, adj_,
                                    x_->adj_, xd_->adj_),
                "log_sum_exp");
   }
@@ -165,7 +165,7 @@ class glm_tangent_dev_vari : public device_vari {
       : device_vari(t), eta_(eta), etad_(etad), alpha_(alpha), alphad_(alphad), a_(a), ad_(ad), y_(y),
         out2_(amd::alloc_doubles(2)) {}
   void chain() override {
-    amd::check(smg_glm_tangent_rev(amd::ctx(), eta_->val_, a_, etad_->val_, ad_, y_, (long long)eta_->size(), adj_,
+    amd::check(smg_glm_tangent_rev(amd::ctx(), eta_->val(), a_, etad_->val(), ad_, y_, (long long)eta_->size(), adj_,
                                    eta_->adj_, etad_->adj_, out2_),
                "bernoulli_logit_glm_lpmf");
     if (alpha_) add_pending_adjoint(alpha_, out2_);
@@ -335,18 +335,18 @@ class chol_tangent_dev_vari : public device_vari {
     const double* Wf = L_->sink_ ? L_->sink_->inverse_factor() : nullptr;
     if (Wf) {
       W_ = const_cast<double*>(Wf);  // (read only)
-      amd::check(smg_chol_tangent_fwd_w(amd::ctx(), L_->val_, n, W_, Ad_->val_, n, n, Wt_, Y_, P_, Ld_->val_, n),
+      amd::check(smg_chol_tangent_fwd_w(amd::ctx(), L_->val(), n, W_, Ad_->val(), n, n, Wt_, Y_, P_, Ld_->raw_val(), n),
                  "cholesky_decompose");
       return;
     }
     W_ = amd::alloc_doubles(nn);
-    amd::check(smg_chol_tangent_fwd(amd::ctx(), L_->val_, n, L_->aux_, Ad_->val_, n, n, W_, Wt_, Y_, P_, Ld_->val_, n),
+    amd::check(smg_chol_tangent_fwd(amd::ctx(), L_->val(), n, L_->aux_, Ad_->val(), n, n, W_, Wt_, Y_, P_, Ld_->raw_val(), n),
                "cholesky_decompose");
   }
   void chain() override {
     const int n = L_->rows_;
     double* ws = amd::alloc_doubles(2 * size_t(n) * n);
-    amd::check(smg_chol_tangent_rev(amd::ctx(), L_->val_, n, W_, Wt_, Y_, P_, n, Ld_->adj_, n, n, L_->adj_, n,
+    amd::check(smg_chol_tangent_rev(amd::ctx(), L_->val(), n, W_, Wt_, Y_, P_, n, Ld_->adj_, n, n, L_->adj_, n,
                                     Ad_->adj_, n, ws),
                "cholesky_decompose");
   }

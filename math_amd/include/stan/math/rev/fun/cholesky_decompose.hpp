@@ -21,6 +21,7 @@
 #include <stan/math/amd/matrix.hpp>
 #include <stan/math/rev/core.hpp>
 
+#include <cmath>
 #include <cstdlib>
 #include <sstream>
 #include <stdexcept>
@@ -35,7 +36,7 @@ namespace internal {
 /** B = A + diag(d) over the min(m, n) leading diagonal (prim/mat/fun/add_diag.hpp:20-55):
  * A a device var node or data; d a scalar (var or double) or a device vector
  * (var node or data). */
-class add_diag_dev_vari : public device_vari, public structured_adjoint_sink {
+class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, public deferred_value_source {
  public:
   dev_operand A_;
   dev_matrix_vari* B_;
@@ -47,21 +48,43 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink {
   // cholesky_dev_vari): dep_ deposited in this sweep, exp_ consumed without
   // forming B's dense adjoint (expand_adjoint writes it when read)
   inverse_adjoint dep_, exp_;
+  const double d_;     // the scalar diagonal's value
+  smg_gp_source src_;  // B = K + d I of a GP covariance K, generated from x (deferred values)
+  bool has_src_ = false;
 
   add_diag_dev_vari(const dev_operand& A, double d, vari* d_vi, const dev_operand& dv)
       : device_vari(0.0), A_(A), B_(new dev_matrix_vari(A.rows, A.cols)), d_vi_(d_vi),
         dadj_(d_vi ? amd::alloc_doubles(1) : nullptr), dv_(dv),
-        pos_(ChainableStack::instance_->var_stack_.size() - 1) {
+        pos_(ChainableStack::instance_->var_stack_.size() - 1), d_(d), src_{} {
     if (A.rows == A.cols && !dv.rows) B_->sink_ = this;  // (square, scalar diagonal)
+    // a scalar diagonal on a GP covariance (its values formed or not): B's
+    // values wait for their first reader -- none under cholesky_decompose,
+    // which generates them into its factor's buffer (chol_source)
+    if (amd::deferred_values_enabled() && B_->sink_ == this && A.rows > 0 && A_.vi && A_.vi->sink_ &&
+        std::isfinite(d) && A_.vi->sink_->gp_source(&src_) && src_.n == A.rows) {
+      src_.d = d;
+      has_src_ = true;
+      B_->defer_values(this);
+      return;
+    }
+    form_values(B_);
+  }
+  // the forward: A's values are forced first
+  void form_values(dev_matrix_vari*) override {
     smg_ctx* c = amd::ctx();
-    const int m = A.rows, n = A.cols, k = m < n ? m : n;
+    const int m = A_.rows, n = A_.cols, k = m < n ? m : n;
     const double* dvec = dv_.rows ? dv_.val() : nullptr;
     if (m == n) {
-      amd::check(smg_add_diag_fwd(c, A_.val(), m, m, d, dvec, B_->val_, m), "add_diag");
+      amd::check(smg_add_diag_fwd(c, A_.val(), m, m, d_, dvec, B_->raw_val(), m), "add_diag");
     } else if (m && n) {  // copy, then the k x k leading block in place
-      amd::check(smg_memcpy_d2d(c, B_->val_, A_.val(), size_t(m) * n * sizeof(double)), "add_diag");
-      amd::check(smg_add_diag_fwd(c, B_->val_, m, k, d, dvec, B_->val_, m), "add_diag");
+      amd::check(smg_memcpy_d2d(c, B_->raw_val(), A_.val(), size_t(m) * n * sizeof(double)), "add_diag");
+      amd::check(smg_add_diag_fwd(c, B_->raw_val(), m, k, d_, dvec, B_->raw_val(), m), "add_diag");
     }
+  }
+  bool chol_source(smg_gp_source* out) override {
+    if (!has_src_ || !B_->values_pending()) return false;
+    *out = src_;
+    return true;
   }
   bool may_write_device_adjoint(const void* node) const override {
     return (A_.vi && node == A_.vi) || (dv_.vi && node == dv_.vi);
@@ -164,7 +187,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
   // would have written: one smg_mvn_cholesky_rev per observation)
   void expand(const double* ws, double adj, int k) const {
     for (int o = 0; o < k; ++o)
-      amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->val_, n_, L_->aux_, n_, ws + 2 * size_t(n_) * o, adj, 1, nullptr,
+      amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->raw_val(), n_, L_->aux_, n_, ws + 2 * size_t(n_) * o, adj, 1, nullptr,
                                       nullptr, L_->adj_, n_),
                  "cholesky_decompose");
   }
@@ -224,7 +247,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
     if (history_of(pos_, n_) == 0) return;
     if (!ws_) ws_ = amd::alloc_doubles(smg_cholesky_mvn_rev_ws_doubles(n_));
     int started = 0;
-    amd::check(smg_cholesky_inv_t_async(amd::ctx(), L_->val_, n_, L_->aux_, n_, ws_, early_ ? 1 : 0, &started),
+    amd::check(smg_cholesky_inv_t_async(amd::ctx(), L_->raw_val(), n_, L_->aux_, n_, ws_, early_ ? 1 : 0, &started),
                "multi_normal_cholesky_lpdf");
     v_ready_ = started != 0;
     c_ready_ = v_ready_ && early_;
@@ -287,7 +310,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
                      "cholesky_decompose");
         } else {
           if (!ws_) ws_ = amd::alloc_doubles(smg_cholesky_mvn_rev_ws_doubles(n_));
-          amd::check(smg_cholesky_mvn_rev(c, L_->val_, n_, L_->aux_, n_, dep_ws_ + n_, dep_k_, 2LL * n_, dep_adj_,
+          amd::check(smg_cholesky_mvn_rev(c, L_->raw_val(), n_, L_->aux_, n_, dep_ws_ + n_, dep_k_, 2LL * n_, dep_adj_,
                                           nullptr, n_, ws_),
                      "cholesky_decompose");
         }
@@ -310,7 +333,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
     // Murray's algorithm overwrites its input and reads only its lower triangle
     double* work = amd::alloc_doubles(nn);
     amd::check(smg_copy_tril(c, n_, n_, L_->adj_, n_, work, n_), "cholesky_decompose");
-    amd::check(smg_cholesky_rev(c, L_->val_, n_, L_->aux_, work, n_, n_, A_->adj_, n_),
+    amd::check(smg_cholesky_rev(c, L_->raw_val(), n_, L_->aux_, work, n_, n_, A_->adj_, n_),
                "cholesky_decompose");
   }
 };
@@ -411,6 +434,12 @@ inline dev_var_matrix cholesky_decompose_impl(const dev_var_matrix& A, var* host
   // follow run while the host builds the next node
   int inv_started = 0;
   const int panels = smg_cholesky_stream_panels(n);
+  // A = add_diag(K, d) of a GP covariance with its values still unformed: the
+  // factorisation's first kernel generates tril(K + d I) from x into L's
+  // buffer in place of the checked copy, and neither K nor A is ever formed
+  smg_gp_source src{};
+  const bool gen = A.vi_->values_pending() && A.vi_->sink_ && A.vi_->sink_->chol_source(&src);
+  const double* Aval = gen ? nullptr : A.val_ptr();
   host_block b{};
   if (host_out && panels <= 64) {
     b.node = L;
@@ -424,8 +453,10 @@ inline dev_var_matrix cholesky_decompose_impl(const dev_var_matrix& A, var* host
     double* stage = static_cast<double*>(smg_host_scratch(c, b.n * sizeof(double)));
     if (!stage) throw std::bad_alloc();
     amd::phase_mark(20);
-    amd::check(smg_cholesky_fwd_checked_mark_stream(c, A.val_ptr(), n, n, L->val_, n, L->aux_, inv_ws, &inv_started,
-                                                    packed, stage, 0),
+    amd::check(gen ? smg_cholesky_fwd_gp_mark_stream(c, &src, L->raw_val(), n, L->aux_, inv_ws, &inv_started, packed,
+                                                     stage, 0)
+                   : smg_cholesky_fwd_checked_mark_stream(c, Aval, n, n, L->raw_val(), n, L->aux_, inv_ws, &inv_started,
+                                                          packed, stage, 0),
                fn);
     amd::phase_mark(0);
     if (verify && !(*verify)()) {  // (rejected: the queued work drains, its results are dropped)
@@ -447,16 +478,22 @@ inline dev_var_matrix cholesky_decompose_impl(const dev_var_matrix& A, var* host
       amd::phase_mark(3 + 2 * p);
     }
   } else if (want_w) {
-    amd::check(smg_cholesky_fwd_checked_mark_winv(c, A.val_ptr(), n, n, L->val_, n, L->aux_, inv_ws, &inv_started),
+    amd::check(gen ? smg_cholesky_fwd_gp_mark_winv(c, &src, L->raw_val(), n, L->aux_, inv_ws, &inv_started)
+                   : smg_cholesky_fwd_checked_mark_winv(c, Aval, n, n, L->raw_val(), n, L->aux_, inv_ws, &inv_started),
                fn);
   } else if (inv_ws) {
-    amd::check(smg_cholesky_fwd_checked_mark_inv(c, A.val_ptr(), n, n, L->val_, n, L->aux_, inv_ws, &inv_started), fn);
+    amd::check(gen ? smg_cholesky_fwd_gp_mark_inv(c, &src, L->raw_val(), n, L->aux_, inv_ws, &inv_started)
+                   : smg_cholesky_fwd_checked_mark_inv(c, Aval, n, n, L->raw_val(), n, L->aux_, inv_ws, &inv_started),
+               fn);
   } else {
-    amd::check(smg_cholesky_fwd_checked_mark(c, A.val_ptr(), n, n, L->val_, n, L->aux_), fn);
+    amd::check(gen ? smg_cholesky_fwd_gp_mark(c, &src, L->raw_val(), n, L->aux_)
+                   : smg_cholesky_fwd_checked_mark(c, Aval, n, n, L->raw_val(), n, L->aux_),
+               fn);
   }
   int st = 0;
   amd::check(smg_status_mark_wait(c, &st), fn);
   amd::phase_mark(30);
+  // (a generated A is formed here, by its own kernels, for the message's elements)
   if (st & SMG_ERR_NOT_SYMMETRIC) internal::throw_not_symmetric_dev(fn, "A", A.val_ptr(), n);
   if (st) amd::throw_status(st, fn, "m");
   auto* node = new internal::cholesky_dev_vari(A.vi_, L);

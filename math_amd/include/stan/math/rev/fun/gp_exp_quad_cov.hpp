@@ -9,6 +9,11 @@
 // value K_ij = sigma^2 exp(-(x_i - x_j)^2 / (2 l^2)) and adjoint
 //   l' += sum_lower Kadj K d^2 / l^3,  sigma' += 2 (sum_lower Kadj K + sum_diag Kadj K) / sigma
 // (:96-112), with the whole matrix on the device (kernels: smg_gp_exp_quad_cov_*).
+//
+// K's values are deferred (dev_matrix_vari::val()): the forward kernel runs
+// when they are first read.  Under add_diag -> cholesky_decompose nothing
+// reads them: the factorisation generates K + d I from x straight into the
+// factor's buffer and the inverse-form reverse recomputes K_ij from x.
 
 #include <stan/math/amd/matrix.hpp>
 #include <stan/math/rev/core.hpp>
@@ -33,7 +38,7 @@ inline void gp_check_positive(const char* fn, const char* name, double v) {
 // The node of every covariance family of the GP path (family_: smg_gp_family;
 // gp_exponential_cov / gp_matern32_cov / gp_matern52_cov in gp_matern_cov.hpp
 // build it with theirs): the families differ only in the C entries called.
-class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_sink {
+class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_sink, public deferred_value_source {
  public:
   const int family_;
   const char* fn_;   // the function's name in error messages
@@ -67,10 +72,32 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
         out2_(amd::alloc_doubles(2)),
         pos_(ChainableStack::instance_->var_stack_.size() - 1) {
     K_->sink_ = this;
+    if (amd::deferred_values_enabled())
+      K_->defer_values(this);
+    else
+      form_values(K_);
+  }
+
+  // the forward (x_, sigma, l live as long as the tape)
+  void form_values(dev_matrix_vari*) override {
     amd::check(family_ == SMG_GP_EXP_QUAD
-                   ? smg_gp_exp_quad_cov_nd_fwd(amd::ctx(), x_, D_, n_, sigma_d_, l_d_, K_->val_, n_)
-                   : smg_gp_cov_fwd(amd::ctx(), family_, x_, D_, n_, sigma_d_, l_d_, K_->val_, n_),
+                   ? smg_gp_exp_quad_cov_nd_fwd(amd::ctx(), x_, D_, n_, sigma_d_, l_d_, K_->raw_val(), n_)
+                   : smg_gp_cov_fwd(amd::ctx(), family_, x_, D_, n_, sigma_d_, l_d_, K_->raw_val(), n_),
                fn_);
+  }
+
+  // what a generator of K's values needs (d left 0); false for hyperparameters
+  // the eager kernels are left to deal with
+  bool gp_source(smg_gp_source* out) override {
+    if (!std::isfinite(sigma_d_) || !std::isfinite(l_d_)) return false;
+    out->family = family_;
+    out->D = D_;
+    out->n = n_;
+    out->x = x_;
+    out->sigma = sigma_d_;
+    out->l = l_d_;
+    out->d = 0.0;
+    return true;
   }
 
   bool may_write_device_adjoint(const void*) const override { return false; }  // (host scalars only)
@@ -86,12 +113,17 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
     if (d.n != n_) return false;
     if (dep_.C && dep_.sweep == ChainableStack::instance_->sweep_) return false;
     double* const out2 = (sigma_vi_ || l_vi_) ? out2_ : nullptr;
-    amd::check(family_ == SMG_GP_EXP_QUAD
-                   ? smg_gp_inverse_adjoint(amd::ctx(), d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->val_, n_, x_, D_,
-                                            sigma_d_, l_d_, dadj, out2)
-                   : smg_gp_cov_inverse_adjoint(amd::ctx(), family_, d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->val_, n_,
-                                                x_, D_, sigma_d_, l_d_, dadj, out2),
-               fn_);
+    if (K_->values_pending())  // K_ij recomputed from x: the values stay unformed
+      amd::check(smg_gp_cov_inverse_adjoint_x(amd::ctx(), family_, d.C, n_, n_, d.s, d.k, d.ss, d.adj, x_, D_, sigma_d_,
+                                              l_d_, dadj, out2),
+                 fn_);
+    else
+      amd::check(family_ == SMG_GP_EXP_QUAD
+                     ? smg_gp_inverse_adjoint(amd::ctx(), d.C, n_, n_, d.s, d.k, d.ss, d.adj, K_->raw_val(), n_, x_, D_,
+                                              sigma_d_, l_d_, dadj, out2)
+                     : smg_gp_cov_inverse_adjoint(amd::ctx(), family_, d.C, n_, n_, d.s, d.k, d.ss, d.adj,
+                                                  K_->raw_val(), n_, x_, D_, sigma_d_, l_d_, dadj, out2),
+                 fn_);
     dep_ = d;
     return true;
   }

@@ -12,7 +12,9 @@
 // The node is gp_exp_quad_cov's (rev/fun/gp_exp_quad_cov.hpp) with another
 // family: K on the device (smg_gp_cov_fwd), the GP marginal's inverse-form
 // adjoint through add_diag (smg_gp_cov_inverse_adjoint), the dense reverse
-// (smg_gp_cov_rev) when K has another consumer.
+// (smg_gp_cov_rev) when K has another consumer.  K's values are deferred as
+// gp_exp_quad_cov's are: formed when first read, never under add_diag ->
+// cholesky_decompose (the factorisation generates them from x).
 //
 // Argument checks, in this order: every x entry is not NaN ("<fn>: x is nan,
 // but must not be nan!"), sigma is positive and finite under the name

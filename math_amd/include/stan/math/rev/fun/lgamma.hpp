@@ -39,14 +39,14 @@ class unary_special_dev_vari : public device_vari {
   explicit unary_special_dev_vari(dev_matrix_vari* x)
       : device_vari(0.0), x_(x), y_(new dev_matrix_vari(x->rows_, x->cols_)) {
     const long long n = (long long)x_->size();
-    amd::check(OP == 0 ? smg_lgamma_fwd(amd::ctx(), x_->val_, n, y_->val_)
-                       : smg_digamma_fwd(amd::ctx(), x_->val_, n, y_->val_),
+    amd::check(OP == 0 ? smg_lgamma_fwd(amd::ctx(), x_->val(), n, y_->raw_val())
+                       : smg_digamma_fwd(amd::ctx(), x_->val(), n, y_->raw_val()),
                OP == 0 ? "lgamma" : "digamma");
   }
   void chain() override {
     const long long n = (long long)x_->size();
-    amd::check(OP == 0 ? smg_lgamma_rev(amd::ctx(), x_->val_, n, y_->adj_, x_->adj_)
-                       : smg_digamma_rev(amd::ctx(), x_->val_, n, y_->adj_, x_->adj_),
+    amd::check(OP == 0 ? smg_lgamma_rev(amd::ctx(), x_->val(), n, y_->adj_, x_->adj_)
+                       : smg_digamma_rev(amd::ctx(), x_->val(), n, y_->adj_, x_->adj_),
                OP == 0 ? "lgamma" : "digamma");
   }
 };

@@ -33,11 +33,11 @@ class mdivide_left_tri_dev_vari : public device_vari {
     // latency-bound persistent solve
     if (lower_ && B_.cols == 1 && B_.rows % 64 == 0 && A_.vi && A_.vi->sink_) W_ = A_.vi->sink_->inverse_factor();
     if (W_) {
-      amd::check(smg_trmv_inv(amd::ctx(), 0, W_, A_.rows, B_.rows, B_.val(), C_->val_), "mdivide_left_tri");
+      amd::check(smg_trmv_inv(amd::ctx(), 0, W_, A_.rows, B_.rows, B_.val(), C_->raw_val()), "mdivide_left_tri");
       return;
     }
     amd::check(smg_mdivide_left_tri_aux_fwd(amd::ctx(), lower_, A_.val(), A_.rows, aux(), B_.val(), B_.rows,
-                                            B_.rows, B_.cols, C_->val_, C_->rows_),
+                                            B_.rows, B_.cols, C_->raw_val(), C_->rows_),
                "mdivide_left_tri");
   }
   // A Cholesky factor carries its diagonal-block inverses (aux_): the
@@ -49,11 +49,11 @@ class mdivide_left_tri_dev_vari : public device_vari {
     if (W_) {  // ws = W^T Cadj;  Aadj (lower) -= ws C^T;  Badj += ws  (:104-123)
       smg_ctx* c = amd::ctx();
       amd::check(smg_trmv_inv(c, 1, W_, A_.rows, m, C_->adj_, ws), "mdivide_left_tri");
-      if (A_.adj()) amd::check(smg_rank1_lower(c, m, -1.0, ws, C_->val_, A_.adj(), A_.rows), "mdivide_left_tri");
+      if (A_.adj()) amd::check(smg_rank1_lower(c, m, -1.0, ws, C_->raw_val(), A_.adj(), A_.rows), "mdivide_left_tri");
       if (B_.adj()) amd::check(smg_axpy(c, (long long)m, 1.0, ws, 1, B_.adj(), 1), "mdivide_left_tri");
       return;
     }
-    amd::check(smg_mdivide_left_tri_aux_rev(amd::ctx(), lower_, A_.val(), A_.rows, aux(), C_->val_, m,
+    amd::check(smg_mdivide_left_tri_aux_rev(amd::ctx(), lower_, A_.val(), A_.rows, aux(), C_->raw_val(), m,
                                             C_->adj_, m, m, n, A_.adj(), A_.rows, B_.adj(), m, ws),
                "mdivide_left_tri");
   }

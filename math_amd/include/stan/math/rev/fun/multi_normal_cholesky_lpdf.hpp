@@ -50,7 +50,7 @@ class mvn_cholesky_dev_vari : public device_vari {
     // a cholesky_decompose factor takes the lower-only partials unexpanded
     // (rev/fun/cholesky_decompose.hpp: its reverse then has a closed form)
     deposited_ = lower_only && L_->sink_ && L_->sink_->take_mvn_adjoint(this, ws_, adj_);
-    amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->val_, n_, L_->aux_, n_, ws_, adj_, lower_only,
+    amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->val(), n_, L_->aux_, n_, ws_, adj_, lower_only,
                                     y_ ? y_->adj_ : nullptr, mu_ ? mu_->adj_ : nullptr,
                                     deposited_ ? nullptr : L_->adj_, n_),
                "multi_normal_cholesky_lpdf");

@@ -76,17 +76,17 @@ class multiply_dev_vari : public device_vari {
                 A.rows % 64 == 0) {
     smg_ctx* c = amd::ctx();
     if (lowvec_) {
-      amd::check(smg_trmv_inv(c, 0, A_.val(), A_.rows, A_.rows, B_.val(), C_->val_), "multiply");
+      amd::check(smg_trmv_inv(c, 0, A_.val(), A_.rows, A_.rows, B_.val(), C_->raw_val()), "multiply");
       return;
     }
     if (gram_) {
       amd::check(smg_gemm(c, 0, 1, 1, A_.rows, A_.rows, A_.cols, 1.0, A_.val(), A_.rows, A_.val(), A_.rows, 0.0,
-                          C_->val_, C_->rows_),
+                          C_->raw_val(), C_->rows_),
                  "multiply");
-      amd::check(smg_sym_from_lower(c, C_->rows_, C_->val_, C_->rows_), "multiply");
+      amd::check(smg_sym_from_lower(c, C_->rows_, C_->raw_val(), C_->rows_), "multiply");
       return;
     }
-    amd::check(smg_multiply_fwd(c, A_.val(), A_.rows, B_.val(), B_.rows, A_.rows, A_.cols, B_.cols, C_->val_,
+    amd::check(smg_multiply_fwd(c, A_.val(), A_.rows, B_.val(), B_.rows, A_.rows, A_.cols, B_.cols, C_->raw_val(),
                                 C_->rows_),
                "multiply");
   }
@@ -129,8 +129,8 @@ class scale_dev_vari : public device_vari {
         B_(new dev_matrix_vari(A.rows, A.cols)) {
     smg_ctx* x = amd::ctx();
     const long long n = (long long)A.rows * A.cols;
-    amd::check(smg_memset(x, B_->val_, 0, size_t(n) * sizeof(double)), "multiply");
-    amd::check(smg_axpy(x, n, c_, A_.val(), 1, B_->val_, 1), "multiply");
+    amd::check(smg_memset(x, B_->raw_val(), 0, size_t(n) * sizeof(double)), "multiply");
+    amd::check(smg_axpy(x, n, c_, A_.val(), 1, B_->raw_val(), 1), "multiply");
   }
   void chain() override {
     smg_ctx* x = amd::ctx();
@@ -151,7 +151,7 @@ class transpose_dev_vari : public device_vari {
   explicit transpose_dev_vari(dev_matrix_vari* A)
       : device_vari(0.0), A_(A), B_(new dev_matrix_vari(A->cols_, A->rows_)) {
     B_->transpose_of_ = A;
-    amd::check(smg_transpose(amd::ctx(), A_->rows_, A_->cols_, A_->val_, A_->rows_, B_->val_,
+    amd::check(smg_transpose(amd::ctx(), A_->rows_, A_->cols_, A_->val(), A_->rows_, B_->raw_val(),
                              B_->rows_, 0.0),
                "transpose");
   }

@@ -70,7 +70,7 @@ class mdivide_left_spd_dev_vari : public device_vari {
     smg_ctx* c = amd::ctx();
     L_ = amd::alloc_doubles(size_t(m) * m);
     aux_ = amd::alloc_doubles(size_t(smg_cholesky_aux_doubles(m)));
-    amd::check(smg_mdivide_left_spd_fwd(c, A_.val(), m, B_.val(), m, m, B_.cols, L_, aux_, C_->val_, m),
+    amd::check(smg_mdivide_left_spd_fwd(c, A_.val(), m, B_.val(), m, m, B_.cols, L_, aux_, C_->raw_val(), m),
                fn);
     int st = 0;
     amd::check(smg_status(c, &st), fn);
@@ -85,7 +85,7 @@ class mdivide_left_spd_dev_vari : public device_vari {
     const int m = B_.rows, n = B_.cols;
     if (!A_.adj() && !B_.adj()) return;
     double* ws = amd::alloc_doubles(size_t(m) * n);
-    amd::check(smg_mdivide_left_spd_rev(amd::ctx(), L_, aux_, m, n, C_->val_, m, C_->adj_, m, A_.adj(), m,
+    amd::check(smg_mdivide_left_spd_rev(amd::ctx(), L_, aux_, m, n, C_->raw_val(), m, C_->adj_, m, A_.adj(), m,
                                         B_.adj(), m, ws),
                "mdivide_left_spd");
   }
@@ -123,13 +123,13 @@ class mlt_self_transpose_dev_vari : public device_vari {
       : device_vari(0.0), L_(L), C_(new dev_matrix_vari(L->rows_, L->rows_)) {
     const int K = L->rows_, J = L->cols_;
     double* ws = amd::alloc_doubles(size_t(K) * (J > 0 ? J : 1));
-    amd::check(smg_multiply_lower_tri_self_transpose_fwd(amd::ctx(), L_->val_, K, K, J, C_->val_, K, ws),
+    amd::check(smg_multiply_lower_tri_self_transpose_fwd(amd::ctx(), L_->val(), K, K, J, C_->raw_val(), K, ws),
                "multiply_lower_tri_self_transpose");
   }
   void chain() override {
     const int K = L_->rows_, J = L_->cols_;
     double* ws = amd::alloc_doubles(size_t(2) * K * J + size_t(K) * K);
-    amd::check(smg_multiply_lower_tri_self_transpose_rev(amd::ctx(), L_->val_, K, K, J, C_->adj_, K,
+    amd::check(smg_multiply_lower_tri_self_transpose_rev(amd::ctx(), L_->val(), K, K, J, C_->adj_, K,
                                                          L_->adj_, K, ws),
                "multiply_lower_tri_self_transpose");
   }
@@ -146,7 +146,7 @@ class quad_form_sym_dev_vari : public device_vari {
         sym_adj_(A.vi && B.vi ? 1 : 0) {
     const int M = B.rows, N = B.cols;
     double* ws = amd::alloc_doubles(size_t(M) * N + size_t(N) * N);
-    amd::check(smg_quad_form_sym_fwd(amd::ctx(), A_.val(), M, B_.val(), M, M, N, C_->val_, N, ws),
+    amd::check(smg_quad_form_sym_fwd(amd::ctx(), A_.val(), M, B_.val(), M, M, N, C_->raw_val(), N, ws),
                "quad_form_sym");
   }
   void chain() override {

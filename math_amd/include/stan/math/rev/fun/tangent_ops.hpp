@@ -30,7 +30,7 @@ class gp_tangent_dev_vari : public device_vari {
       : device_vari(0.0), x_(x), n_(n), s_(s.val()), l_(l.val()), ds_(ds.val()), dl_(dl.val()),
         vis_{s.vi_, l.vi_, ds.vi_, dl.vi_}, K_(new dev_matrix_vari(n, n)),
         out4_(amd::alloc_doubles(4)) {
-    amd::check(smg_gp_exp_quad_cov_tangent_fwd(amd::ctx(), x_, n_, s_, l_, ds_, dl_, K_->val_, n_),
+    amd::check(smg_gp_exp_quad_cov_tangent_fwd(amd::ctx(), x_, n_, s_, l_, ds_, dl_, K_->raw_val(), n_),
                "gp_exp_quad_cov");
   }
   void chain() override {
@@ -49,7 +49,7 @@ class phi_dev_vari : public device_vari {
   dev_matrix_vari* Y_;
   explicit phi_dev_vari(dev_matrix_vari* X)
       : device_vari(0.0), X_(X), Y_(new dev_matrix_vari(X->rows_, X->cols_, dev_structure::lower)) {
-    amd::check(smg_phi(amd::ctx(), X_->rows_, X_->val_, X_->rows_, Y_->val_, Y_->rows_, 0), "phi");
+    amd::check(smg_phi(amd::ctx(), X_->rows_, X_->val(), X_->rows_, Y_->raw_val(), Y_->rows_, 0), "phi");
   }
   void chain() override {
     amd::check(smg_phi(amd::ctx(), X_->rows_, Y_->adj_, Y_->rows_, X_->adj_, X_->rows_, 1), "phi");
@@ -64,8 +64,8 @@ class dot_dev_vari : public device_vari {
   void chain() override {
     smg_ctx* c = amd::ctx();
     const long long n = (long long)x_->size();
-    amd::check(smg_axpy(c, n, adj_, y_->val_, 1, x_->adj_, 1), "dot_product");
-    amd::check(smg_axpy(c, n, adj_, x_->val_, 1, y_->adj_, 1), "dot_product");
+    amd::check(smg_axpy(c, n, adj_, y_->val(), 1, x_->adj_, 1), "dot_product");
+    amd::check(smg_axpy(c, n, adj_, x_->val(), 1, y_->adj_, 1), "dot_product");
   }
 };
 
@@ -75,7 +75,7 @@ class diag_ratio_dev_vari : public device_vari {
   dev_matrix_vari* B_;
   diag_ratio_dev_vari(double v, dev_matrix_vari* A, dev_matrix_vari* B) : device_vari(v), A_(A), B_(B) {}
   void chain() override {
-    amd::check(smg_diag_ratio_rev(amd::ctx(), A_->rows_, A_->val_, A_->rows_, B_->val_, B_->rows_,
+    amd::check(smg_diag_ratio_rev(amd::ctx(), A_->rows_, A_->val(), A_->rows_, B_->val(), B_->rows_,
                                   adj_, A_->adj_, A_->rows_, B_->adj_, B_->rows_),
                "diag_ratio_sum");
   }

@@ -67,7 +67,7 @@ void gradient(const F& f, const dev_data<double>& x, double& fx, double* grad_de
     smg_ctx* c = amd::ctx();
     auto* leaf = new dev_matrix_vari(x.rows(), x.cols());
     const size_t n = leaf->size();
-    amd::check(smg_memcpy_d2d(c, leaf->val_, x.data(), n * sizeof(double)), "gradient");
+    amd::check(smg_memcpy_d2d(c, leaf->raw_val(), x.data(), n * sizeof(double)), "gradient");
     var fx_var = f(dev_var_matrix(leaf));
     fx = fx_var.val();
     grad(fx_var.vi_);
