@@ -139,6 +139,14 @@ int smg_set_inv_block_mode(smg_ctx* ctx, int mode);
 /* 1 when mode 0 takes the one-launch form for an n x n factorisation on this
  * device, 0 if not, -1 on a null ctx or n <= 0 */
 int smg_inv_block_fused(smg_ctx* ctx, int n);
+/* dev / test hook: how the 64 x 64 GEMM tile stages its operands
+ * mode 0: by policy (LDS-DMA for the eligible products of the families and
+ *         tile counts where it measured faster, else through registers);
+ * mode 1: always through registers;
+ * mode 2: LDS-DMA for every eligible product (full or lower C; m, n multiples
+ *         of 64, k of 32; even leading dimensions; 16-byte aligned A, B, C;
+ *         C aliasing no operand), whatever its tile count */
+int smg_set_gemm_stage_mode(smg_ctx* ctx, int mode);
 
 /* ------------------------------------------------------- instrumentation ---
  * HIP-event timing of the kernel families on the context stream (used by
@@ -186,6 +194,11 @@ int smg_gemm(smg_ctx* ctx, int transA, int transB, int uplo, int m, int n, int k
 #define SMG_TRI_B_UPPER 8
 int smg_gemm_tri(smg_ctx* ctx, int transA, int transB, int uplo, int tri, int m, int n, int k, double alpha,
                  const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc);
+/* smg_gemm_tri with beta taken as 0 (C not read) for C's rows from bz on
+ * (bz > 0) or its columns from -bz on (bz < 0): the first contribution to that
+ * region of an accumulated product.  bz must be a multiple of 128. */
+int smg_gemm_bz(smg_ctx* ctx, int transA, int transB, int uplo, int tri, int m, int n, int k, double alpha,
+                const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc, int bz);
 
 /* ---------------------------------------------------------- functors ---- */
 

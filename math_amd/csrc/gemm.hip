@@ -14,6 +14,10 @@
 // Global->LDS staging goes through registers (one stage of prefetch for the
 // 128 x 128 tile, two for the small tiles) into double-buffered LDS; the
 // beta * C operand of the epilogue is fetched before the K loop.
+// The 64 x 64 tile has a second staging path for whole-tile, aligned products
+// (dma_eligible): 16-byte LDS-DMA loads straight into the same swizzled
+// images (the swizzle applied to the source address), no staging registers,
+// K stages of 32 in two LDS buffers (8 waves) or of 16 in three (4 waves).
 // Split-K writes fixed-order partial slabs reduced by a second kernel, so the
 // result is bitwise deterministic run to run.
 #include "smg_internal.h"
@@ -26,6 +30,31 @@
 #endif
 #ifndef SMG_GEMM_KS2_MAX
 #define SMG_GEMM_KS2_MAX 1536  // largest 64 x 64 tile count that takes the 8-wave variant
+#endif
+// The DMA-staged 64 x 64 kernel: K stage depth and LDS buffers of its 4-wave
+// (1) and 8-wave (2) forms, the largest tile count that takes the 8-wave one,
+// the fewest tiles the policy gives it, and the families it gives it
+// (1: NT lower, 2: TN lower, 4: NN full, 8: TN full, 16: NN lower)
+#ifndef SMG_GEMM_DMA_BK1
+#define SMG_GEMM_DMA_BK1 16
+#endif
+#ifndef SMG_GEMM_DMA_NB1
+#define SMG_GEMM_DMA_NB1 3
+#endif
+#ifndef SMG_GEMM_DMA_BK2
+#define SMG_GEMM_DMA_BK2 32
+#endif
+#ifndef SMG_GEMM_DMA_NB2
+#define SMG_GEMM_DMA_NB2 2
+#endif
+#ifndef SMG_GEMM_DMA_KS2_MAX
+#define SMG_GEMM_DMA_KS2_MAX 512
+#endif
+#ifndef SMG_GEMM_DMA_MIN_TILES
+#define SMG_GEMM_DMA_MIN_TILES 136
+#endif
+#ifndef SMG_GEMM_DMA_FAMILIES
+#define SMG_GEMM_DMA_FAMILIES 31
 #endif
 #ifndef SMG_GEMM_NR64
 #define SMG_GEMM_NR64 2
@@ -47,6 +76,11 @@ struct lds_layout<BM, BK, false> {  // [k][BM], row index ^ 16 on odd k
   static_assert(BM % 32 == 0, "BM");
   static constexpr int size = BK * BM;
   __device__ static int at(int i, int kk) { return kk * BM + (i ^ ((kk & 1) << 4)); }
+  // the element stored at position p (the inverse of at; p even: p + 1 holds (i + 1, kk))
+  __device__ static void from(int p, int& i, int& kk) {
+    kk = p / BM;
+    i = (p % BM) ^ ((kk & 1) << 4);
+  }
 };
 template <int BM, int BK>
 struct lds_layout<BM, BK, true> {  // [BM][BK], k index ^ f(row)
@@ -55,7 +89,37 @@ struct lds_layout<BM, BK, true> {  // [BM][BK], k index ^ f(row)
   __device__ static int at(int i, int kk) {
     return i * BK + (kk ^ (BK == 16 ? (i & 14) : ((i & 15) << 1)));
   }
+  // (p even: p + 1 holds (i, kk + 1); both swizzles leave bit 0 alone)
+  __device__ static void from(int p, int& i, int& kk) {
+    i = p / BK;
+    kk = (p % BK) ^ (BK == 16 ? (i & 14) : ((i & 15) << 1));
+  }
 };
+
+// One 16-byte LDS-DMA load per lane: the wave's 64 lanes fill 1 KiB of LDS
+// from `lds` (a wave-uniform byte address) on in lane order, each from its own
+// global address g (16-byte aligned).  No register destination, and the
+// compiler does not count it: the issuing wave waits with dma_wait_barrier.
+// (M0 holds the LDS base only inside the statement.)
+__device__ __forceinline__ void dma16(const double* g, unsigned lds) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(g), "s"(lds)
+      : "memory");
+}
+
+// Leave at most N of this wave's loads in flight, retire its fragment reads,
+// then the workgroup barrier: behind it every wave's DMA issued before its
+// last N loads has landed in LDS, and every wave is done reading the buffer
+// that is staged next.  A raw barrier: __syncthreads() would drain to vmcnt(0).
+template <int N>
+__device__ __forceinline__ void dma_wait_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
 
 // compile-time unrolled loop: f(std::integral_constant<int, 0>) .. f(<N - 1>)
 template <int I, int N, typename F>
@@ -168,7 +232,11 @@ __device__ __forceinline__ void tri_decode_grouped(int t, int T, int& bi, int& b
 // alternate halves of every K stage and their accumulators are summed in the
 // epilogue -- twice the waves per CU for grids that cover the CUs only once
 // or twice)
-template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1>
+// NB: 0 = operands staged through registers; 2 or 3 = staged by LDS-DMA into
+// NB LDS buffers (64 x 64 tile only).  That path has no bounds handling: the
+// host takes it only for whole tiles, K ranges in whole stages and 16-byte
+// aligned operand pairs (dma_eligible).
+template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1, int NB = 0>
 __global__ __launch_bounds__(256 * KS) void k_gemm(
     int m, int n, int k, double alpha, const double* __restrict__ A, int lda,
     const double* __restrict__ B, int ldb, double beta, double* __restrict__ C,
@@ -193,7 +261,7 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
   // operand tiles are double-buffered in LDS (one barrier per K stage)
   constexpr int NR = BM == 128 ? 1 : (BM == 64 ? SMG_GEMM_NR64 : SMG_GEMM_NR32);
   constexpr int STAGE = LA::size + LB::size;
-  constexpr int OPS = 2 * STAGE;
+  constexpr int OPS = (NB ? NB : 2) * STAGE;
   constexpr int ECH = (BM * BN + BN <= OPS) ? BN : 32;
   constexpr int POOL = (OPS > (BM + 1) * ECH) ? OPS : (BM + 1) * ECH;
   __shared__ double pool[POOL];
@@ -332,8 +400,10 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
   // stages past the end are masked to zero): a conditional load would make
   // the waitcnt pass assume the worst on the loop back-edge and wait for ALL
   // outstanding loads at each LDS store, i.e. no prefetch at all
+  if constexpr (NB == 0) {
 #pragma unroll
-  for (int j = 0; j < NR; ++j) gload(j, j);
+    for (int j = 0; j < NR; ++j) gload(j, j);
+  }
   // epilogue operand in flight during the K loop (small tiles only: the
   // 128 x 128 tile would double its register count); coalesced mapping
   // e = tid + 256 q -> (i = e % BM, j = e / BM), the same as the store
@@ -371,6 +441,7 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
           acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
     }
   };
+  if constexpr (NB == 0) {
   // stage s computes from LDS buffer s & 1 while stage s + 1 is stored into
   // the other buffer and stage s + 1 + NR is issued into the freed registers
   // (one barrier per stage); the loop is unrolled by two so that every
@@ -399,6 +470,69 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
   smg_static_for<U - 1>([&](auto uc) {
     if (s0 + decltype(uc)::value < nst) body(s0 + decltype(uc)::value, uc);
   });
+  } else {
+    // LDS-DMA staging.  The LDS image of a tile is filled linearly, 1 KiB per
+    // wave instruction (dma16); lane l of wave w writes doubles p, p + 1 with
+    // p = 128 (q NW + w) + 2 l in its q-th instruction, and fetches the
+    // element pair that lds_layout stores there (the swizzle is applied to
+    // the source address).  Instruction q + 1 is NW 1-KiB pieces further on:
+    // 2 NW k-rows (m-contiguous image: the same k parity, so the same
+    // swizzle) or 128 NW / BK tile rows (k-contiguous image: a multiple of
+    // 16, so the same swizzle) -- a wave-uniform pointer step.
+    constexpr int NW = 4 * KS;         // waves
+    constexpr int QA = BK / 2 / NW;    // DMA instructions per wave, operand tile and stage
+    constexpr int L = 2 * QA;          // ... per stage
+    static_assert(BM == 64 && BN == 64 && BK / 2 % NW == 0 && (NB == 2 || NB == 3), "DMA staging: 64 x 64 tile");
+    static_assert(AK ? (128 * NW / BK) % 16 == 0 : true, "DMA staging: swizzle period");
+    static_assert(NB * STAGE * 8 <= 65536, "DMA staging: LDS");
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const double *pa, *pb;
+    {
+      int i, kk;
+      LA::from(wv * 128 + 2 * lane, i, kk);
+      pa = AK ? A + ((size_t)(i0 + i) * lda + kbeg + kk) : A + ((i0 + i) + (size_t)(kbeg + kk) * lda);
+      LB::from(wv * 128 + 2 * lane, i, kk);
+      pb = BKC ? B + ((size_t)(j0 + i) * ldb + kbeg + kk) : B + ((j0 + i) + (size_t)(kbeg + kk) * ldb);
+    }
+    const long long qsa = (long long)(AK ? 128 * NW / BK : 2 * NW) * lda;
+    const long long qsb = (long long)(BKC ? 128 * NW / BK : 2 * NW) * ldb;
+    const long long ssa = AK ? BK : (long long)BK * lda, ssb = BKC ? BK : (long long)BK * ldb;
+    const unsigned ldsw = (unsigned)(size_t)pool + wv * 1024;
+    auto issue = [&](auto bc) {  // the next stage into buffer bc
+      constexpr int buf = decltype(bc)::value;
+#pragma unroll
+      for (int q = 0; q < QA; ++q) dma16(pa + q * qsa, ldsw + (buf * STAGE) * 8 + q * NW * 1024);
+#pragma unroll
+      for (int q = 0; q < QA; ++q) dma16(pb + q * qsb, ldsw + (buf * STAGE + LA::size) * 8 + q * NW * 1024);
+      pa += ssa;
+      pb += ssb;
+    };
+    // Stage st is computed from buffer st % NB.  Before it: wait for this
+    // wave's loads of stage st (with three buffers stage st + 1 stays in
+    // flight across the barrier), barrier, then stage st + NB - 1 into the
+    // buffer stage st - 1 was read from -- every wave finished those reads
+    // before the barrier.  The fragment reads of stage st come after the
+    // barrier that follows the wait for its loads.
+    auto step = [&](int st, auto uc, auto full) {
+      constexpr int u = decltype(uc)::value;
+      constexpr bool FULL = decltype(full)::value;  // stages st + 1 .. st + NB - 1 exist
+      if (NB == 3 && (FULL || st + 1 < nst)) dma_wait_barrier<L>();
+      else dma_wait_barrier<0>();
+      if (FULL || st + NB - 1 < nst) issue(std::integral_constant<int, (u + NB - 1) % NB>{});
+      mma_stage(pool + u * STAGE, pool + u * STAGE + LA::size);
+    };
+    if (nst > 0) {
+      issue(std::integral_constant<int, 0>{});
+      if (NB == 3 && nst > 1) issue(std::integral_constant<int, 1>{});
+      int s0 = 0;
+      for (; s0 + 2 * NB - 1 <= nst; s0 += NB)
+        smg_static_for<NB>([&](auto uc) { step(s0 + decltype(uc)::value, uc, std::true_type{}); });
+      for (; s0 < nst; s0 += NB)
+        smg_static_for<NB>([&](auto uc) {
+          if (s0 + decltype(uc)::value < nst) step(s0 + decltype(uc)::value, uc, std::false_type{});
+        });
+    }
+  }
 
   // epilogue: D layout of v_mfma_f64_16x16x4_f64: reg r of lane l holds
   // row (l>>4) + 4r, col l&15 of the 16x16 tile.  Accumulators go to LDS
@@ -516,7 +650,7 @@ thread_local int t_ldc2 = 0;
 // the beta-zero boundary of the next product (k_gemm's bz; smg_gemm_bz_impl)
 thread_local int t_bz = 0;
 
-template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1>
+template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1, int NB = 0>
 int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
            int lda, const double* B, int ldb, double beta, double* C, int ldc, int batch = 1,
            long long sA = 0, long long sB = 0, long long sC = 0, int tri = 0) {
@@ -534,7 +668,8 @@ int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
   // (triangular operands: every tile has its own K range, no split)
   // (MODE 3 / 4 products -- the symbolic step's, with triangular operands --
   // never split)
-  if (!tri && MODE != 3 && MODE != 4 && batch == 1 && ntiles < target && !covers &&
+  // (the DMA-staged kernel never splits: its K ranges are whole stages)
+  if (NB == 0 && !tri && MODE != 3 && MODE != 4 && batch == 1 && ntiles < target && !covers &&
       k >= 2 * KMIN) {
     splits = smg_ceil_div(target, ntiles);
     const int maxs = k / KMIN;
@@ -575,7 +710,7 @@ int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
       }
     }
   }
-  hipLaunchKernelGGL((k_gemm<BM, BN, BK, TA, TB, MODE, KS>), dim3(ntp * splits, batch), dim3(256 * KS), 0,
+  hipLaunchKernelGGL((k_gemm<BM, BN, BK, TA, TB, MODE, KS, NB>), dim3(ntp * splits, batch), dim3(256 * KS), 0,
                      ctx->stream, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tm,
                      ntiles, kchunk, slab, sA, sB, sC, px, ntp, tri, MODE >= 3 ? t_c2 : nullptr,
                      MODE >= 3 ? t_ldc2 : 0, t_bz);
@@ -616,9 +751,20 @@ inline bool overlaps(const double* X, int ldx, int rows, int cols, const double*
 // buffers within 32 KB per workgroup (four or more workgroups per CU)
 constexpr int BK64 = 16;
 
+// May the product take the DMA-staged 64 x 64 kernel (k_gemm's NB != 0)?
+// Whole tiles, every K range (the triangular cuts are 64-aligned) in whole
+// stages, and element pairs that are 16-byte aligned in every operand.
+inline bool dma_eligible(int m, int n, int k, const double* A, int lda, const double* B, int ldb,
+                         const double* C, int ldc) {
+  constexpr int KQ = SMG_GEMM_DMA_BK1 > SMG_GEMM_DMA_BK2 ? SMG_GEMM_DMA_BK1 : SMG_GEMM_DMA_BK2;
+  return m % 64 == 0 && n % 64 == 0 && k > 0 && k % KQ == 0 && !((lda | ldb | ldc) & 1) &&
+         !(((size_t)A | (size_t)B | (size_t)C) & 15);
+}
+
 template <bool TA, bool TB, int MODE>
 int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
-                  int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri) {
+                  int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri,
+                  bool aliased = false) {
   constexpr bool FULLC = MODE == 0 || MODE == 4;  // every tile of C computed
   // In-place products (C aliases an operand: the blocked TRSMs C = C Dinv,
   // L21 = A21 Dinv^T, X_p = W_p B_p) are race-free only when every workgroup
@@ -634,7 +780,7 @@ int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double*
     // general aliasing: out of place through a workspace, then C = T (+ beta C)
     double* T = smg_ws(ctx, SMG_WS_ALIAS, (size_t)m * n);
     if (!T) return SMG_ERR_OOM;
-    int rc = dispatch_tile<TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, 0.0, T, m, tri);
+    int rc = dispatch_tile<TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, 0.0, T, m, tri, true);
     if (rc) return rc;
     if (beta == 0.0) return smg_copy_impl(ctx, m, n, T, m, C, ldc, 1.0, 0);
     if (beta != 1.0) {
@@ -651,6 +797,31 @@ int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double*
   const long long t64 = smg_ceil_div(m, 64);
   const long long mid_tiles =
       (!FULLC && m == n) ? t64 * (t64 + 1) / 2 : t64 * smg_ceil_div(n, 64);
+  // The DMA-staged 64 x 64 kernel (full and lower C) for the eligible products
+  // of the families, tile counts and K where it measured faster than what
+  // the policy below takes (profiles/gemm_dma_stage_ubench.txt): from
+  // SMG_GEMM_DMA_MIN_TILES tiles on, K >= 512, except the dense full products
+  // large enough for 128 x 128 tiles (with a triangular operand the 64 x 64
+  // grid's longest-K-first order wins there too).  8 waves up to
+  // SMG_GEMM_DMA_KS2_MAX tiles, 4 above.  ctx->gemm_stage 1 never takes it,
+  // 2 takes it for every eligible product (smg_set_gemm_stage_mode).
+  if constexpr (MODE == 0 || MODE == 1) {
+    constexpr int fam = MODE == 1 ? (!TA && TB ? 1 : TA && !TB ? 2 : !TA && !TB ? 16 : 0)
+                                  : (!TA && !TB ? 4 : TA && !TB ? 8 : 0);
+    const bool g128 = FULLC && big_tiles >= (tri ? SMG_GEMM_TRI128_MIN : 256) && k > 128;
+    // (a grid below one tile per CU only while K is short: the long-K ones
+    // need the split or the 4x finer grid, (512,1024,3072) TN 68 vs 102 us)
+    const bool policy = (SMG_GEMM_DMA_FAMILIES & fam) && k >= 512 && !(g128 && !tri) &&
+                        (mid_tiles >= 256 || (mid_tiles >= SMG_GEMM_DMA_MIN_TILES && k <= 1024));
+    const bool want = ctx->gemm_stage == 2 || (ctx->gemm_stage == 0 && policy);
+    if (want && !aliased && dma_eligible(m, n, k, A, lda, B, ldb, C, ldc)) {
+      if (mid_tiles <= SMG_GEMM_DMA_KS2_MAX)
+        return launch<64, 64, SMG_GEMM_DMA_BK2, TA, TB, MODE, 2, SMG_GEMM_DMA_NB2>(ctx, m, n, k, alpha, A, lda, B, ldb,
+                                                                                 beta, C, ldc, 1, 0, 0, 0, tri);
+      return launch<64, 64, SMG_GEMM_DMA_BK1, TA, TB, MODE, 1, SMG_GEMM_DMA_NB1>(ctx, m, n, k, alpha, A, lda, B, ldb,
+                                                                               beta, C, ldc, 1, 0, 0, 0, tri);
+    }
+  }
   // (triangle modes keep 64 x 64 tiles: half the 128-tile grid would sit on
   // the diagonal, and the split-K those few tiles need costs a reduction; at
   // N = K = 4096 the 528-tile 128 triangle -- 2.06 waves over the CUs -- ran
@@ -823,6 +994,14 @@ extern "C" int smg_gemm_tri(smg_ctx* ctx, int ta, int tb, int uplo, int tri, int
     if (lda < (ta ? k : m) || ldb < (tb ? n : k)) return SMG_ERR_ARG;
   }
   return smg_gemm_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
+}
+
+extern "C" int smg_gemm_bz(smg_ctx* ctx, int ta, int tb, int uplo, int tri, int m, int n, int k, double alpha,
+                           const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc,
+                           int bz) {
+  if (!ctx || m <= 0 || n <= 0 || k <= 0 || tri < 0 || tri > 15 || alpha == 0.0) return SMG_ERR_ARG;
+  if (!A || !B || !C || ldc < m || lda < (ta ? k : m) || ldb < (tb ? n : k)) return SMG_ERR_ARG;
+  return smg_gemm_bz_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, bz);
 }
 
 extern "C" int smg_gemm(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k,

@@ -89,6 +89,7 @@ struct smg_ctx {
   long long inv_launches;
   int inv_per_cu, inv_cus;  // k_inv_block512's occupancy per CU and the CUs (-1: not yet queried)
   int inv_mode;      // 1: the block inverses by the six-launch chain (smg_set_inv_block_mode, a test hook)
+  int gemm_stage;    // the 64 x 64 GEMM tile's staging: 0 policy, 1 registers, 2 LDS-DMA where eligible (smg_set_gemm_stage_mode)
   // pinned host scratch
   void* host_scratch;
   size_t host_scratch_size;

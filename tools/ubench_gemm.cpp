@@ -1,5 +1,6 @@
 // Dev microbenchmark: smg_gemm on the shapes of one blocked-Cholesky step
 // (tools/ubench_shapes.h) plus an empty-kernel floor.
+// usage: ubench_gemm [shape index | -1 [stage mode (smg_set_gemm_stage_mode)]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@ int main(int argc, char** argv) {
   smg_ctx* ctx = nullptr;
   smg_ctx_create(0, 1ull << 30, &ctx);
   hipStream_t s = (hipStream_t)smg_ctx_stream(ctx);
+  if (argc > 2 && smg_set_gemm_stage_mode(ctx, atoi(argv[2]))) return 1;
   const int n = 4096;
   double *A, *B, *C;
   hipMalloc(&A, sizeof(double) * n * n);

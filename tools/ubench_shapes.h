@@ -13,12 +13,15 @@ static const ub_shape ub_shapes[] = {
     // forward: (a) next panel's columns (lower trapezoid), (b) the rest (SYRK)
     {"fwd (a) NT lower (3584,512,512)", 0, 1, 1, 3584, 512, 512},
     {"fwd (a) NT lower (2048,512,512)", 0, 1, 1, 2048, 512, 512},
+    {"fwd (a) NT lower (1536,512,512)", 0, 1, 1, 1536, 512, 512},
+    {"fwd (a) NT lower (1024,512,512)", 0, 1, 1, 1024, 512, 512},
     {"fwd (b) SYRK (3072,3072,512)", 0, 1, 1, 3072, 3072, 512},
     {"fwd (b) SYRK (2048,2048,512)", 0, 1, 1, 2048, 2048, 512},
     {"fwd (b) SYRK (1024,1024,512)", 0, 1, 1, 1024, 1024, 512},
     // reverse, block P (J = 512 P, K = J + 512, m = 4096 - K)
     {"rev C*W NN (3072,512,512)", 0, 0, 0, 3072, 512, 512},
     {"rev C*W NN (1536,512,512)", 0, 0, 0, 1536, 512, 512},
+    {"rev C*W NN (1024,512,512)", 0, 0, 0, 1024, 512, 512},
     {"rev B_adj NN (2048,1536,512)", 0, 0, 0, 2048, 1536, 512},
     {"rev B_adj NN (1024,2560,512)", 0, 0, 0, 1024, 2560, 512},
     {"rev B_adj NN (3072,512,512)", 0, 0, 0, 3072, 512, 512},
@@ -27,6 +30,7 @@ static const ub_shape ub_shapes[] = {
     {"rev [R|D] TN (512,3584,512)", 1, 0, 0, 512, 3584, 512},
     {"rev sym TN (512,512,512)", 1, 0, 0, 512, 512, 512},
     {"rev sym NN (512,512,512)", 0, 0, 0, 512, 512, 512},
+    {"rev P*R NN (512,1024,512)", 0, 0, 0, 512, 1024, 512},
     {"rev P*R NN (512,2048,512)", 0, 0, 0, 512, 2048, 512},
     {"rev P*R NN (512,3584,512)", 0, 0, 0, 512, 3584, 512},
     {"big NN (4096,4096,4096)", 0, 0, 0, 4096, 4096, 4096},

@@ -2,15 +2,18 @@
 // K = 512) as the TN product the factorisation issues against the NT product
 // on a transposed copy of W_k (+ the transpose), alone on the device, and the
 // right-looking Y part's NN shape.  Prints us per call and TF/s.
+// usage: ubench_share [stage mode (smg_set_gemm_stage_mode)]
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 #include "../include/smg_hip.h"
 
-int main() {
+int main(int argc, char** argv) {
   smg_ctx* ctx = nullptr;
   if (smg_ctx_create(0, 1ull << 30, &ctx)) return 1;
   hipStream_t s = (hipStream_t)smg_ctx_stream(ctx);
+  if (argc > 1 && smg_set_gemm_stage_mode(ctx, atoi(argv[1]))) return 1;
   const int n = 4096, P = 512;
   double *W, *V, *C;
   hipMalloc(&W, sizeof(double) * n * n);
