@@ -657,6 +657,39 @@ int smg_gp_cov_inverse_adjoint_x(smg_ctx* ctx, int family, const double* C, int 
                                  long long s_stride, double adj, const double* x, int D, double sigma, double l,
                                  double* dadj, double* out2);
 
+/* One length scale per input dimension (ARD): the std::vector<T_l>
+ * length_scale overloads of gp_exp_quad_cov / gp_exponential_cov /
+ * gp_matern32_cov / gp_matern52_cov over D-dimensional points, which the
+ * reference computes as divide_columns(x, l) followed by the kernel of unit
+ * length scale.  Here the same split: z = x / l once (smg_gp_ard_scale), K by
+ * smg_gp_cov_fwd(family, z, D, n, sigma, 1.0, ...) and the generated
+ * factorisation input by an smg_gp_source {x = z, l = 1}; the entries below
+ * are the reverse's 1 + D hyperparameter sums.  With t_d = z_id - z_jd,
+ * r^2 = sum_d t_d^2 and a = c r (c = 1, 1, sqrt 3, sqrt 5):
+ *   dK_ij/dl_d = sigma^2 h(a) t_d^2 / l_d  (i != j),  h = e^{-r^2/2}, e^{-a}/a
+ *   (0 at a = 0), 3 e^{-a}, (5/3)(1 + a) e^{-a}  (gp_family.h).
+ * l: a HOST array of D doubles in every entry, 1 <= D <= SMG_GP_ARD_MAX_D. */
+#define SMG_GP_ARD_MAX_D 64
+/* z (D x n, point i at z + i D) = x_id / l_d, an IEEE division, and in the
+ * same launch zt (NULL skips), its coordinate-major copy (n x D, coordinate d
+ * of point i at zt[d n + i]): what the two reducers below read, their lanes
+ * on consecutive points (measured faster than z at every D). */
+int smg_gp_ard_scale(smg_ctx* ctx, const double* x, int D, int n, const double* l, double* z, double* zt);
+/* out (1 + D doubles, accumulated into) from the full adjoint Kadj (every
+ * position swept once, as smg_gp_cov_rev):
+ *   out[0]     += 2 (sum_{i != j} Kadj_ij K_ij + sum_i Kadj_ii sigma^2) / sigma
+ *   out[1 + d] += sum_{i != j} Kadj_ij dK_ij/dl_d
+ * K_ij recomputed from zt with smg_gp_cov_fwd's per-element expression. */
+int smg_gp_ard_cov_rev(smg_ctx* ctx, int family, const double* zt, int D, int n, double sigma, const double* l,
+                       const double* Kadj, int ldka, double* out);
+/* smg_gp_cov_inverse_adjoint_x for ARD: G = adj Phi(sum_o s_o s_o^T - k C)
+ * over C's lower triangle, dadj = sum_i G_ii, out (1 + D doubles) = the sums
+ * above with G for Kadj.  Written, not accumulated; either may be NULL, and
+ * dadj alone needs neither zt nor l.  Fixed-order reductions (no atomics). */
+int smg_gp_ard_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
+                                   long long s_stride, double adj, const double* zt, int D, double sigma,
+                                   const double* l, double* dadj, double* out);
+
 /* log_sum_exp(vector<var>) (rev/mat/fun/log_sum_exp.hpp:20-53):
  *   fwd: out = max + log(sum exp(x - max)); empty -> -inf; non-finite max -> max
  *   rev: xadj_i += adj * exp(x_i - lse)   (lse, adj: host values of the vari) */

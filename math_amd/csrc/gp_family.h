@@ -13,6 +13,11 @@
 // otherwise.  No derivative divides by d: coincident points give K = s2 and a
 // zero l-derivative.  exp_quad's members are the expressions the kernels had
 // before they were templated (the same bits).
+//
+// One length scale per dimension (ARD, gp_ard.hip): the points are scaled
+// first, z = x / l, and the kernels above run on z with c = coef(1).  With
+// t_d = z_id - z_jd and a = c q:  dK_ij/dl_d = s2 h(a) t_d^2 / l_d,
+//   h = exp(-q / 2) | exp(-a) / a (0 at a = 0) | 3 exp(-a) | (5/3)(1 + a) exp(-a).
 #ifndef SMG_GP_FAMILY_H
 #define SMG_GP_FAMILY_H
 
@@ -40,6 +45,8 @@ struct gp_fam<SMG_GP_EXP_QUAD> {
   // dK/dl = K w(q) scaled by lscale: the fused reducer's weight (it reads K)
   static __device__ __forceinline__ double w(double q, double c) { return q; }
   static __device__ __forceinline__ double lscale(double sl, double l) { return sl / (l * l * l); }
+  // ARD (q from z = x / l, c = coef(1)): dK/dl_d = s2 h t_d^2 / l_d
+  static __device__ __forceinline__ double h(double q, double c) { return exp(-q * c); }
 };
 
 template <>
@@ -56,6 +63,11 @@ struct gp_fam<SMG_GP_EXPONENTIAL> {
   }
   static __device__ __forceinline__ double w(double q, double c) { return q * c; }
   static __device__ __forceinline__ double lscale(double sl, double l) { return sl / l; }
+  // (the one h that divides by a: t_d^2 / a -> 0 with the distance, 0 at a coincident pair)
+  static __device__ __forceinline__ double h(double q, double c) {
+    const double t = q * c;
+    return t > 0.0 ? exp(-t) / t : 0.0;
+  }
 };
 
 template <>
@@ -78,6 +90,7 @@ struct gp_fam<SMG_GP_MATERN32> {
     return t * t / (1.0 + t);
   }
   static __device__ __forceinline__ double lscale(double sl, double l) { return sl / l; }
+  static __device__ __forceinline__ double h(double q, double c) { return 3.0 * exp(-(q * c)); }
 };
 
 template <>
@@ -100,6 +113,10 @@ struct gp_fam<SMG_GP_MATERN52> {
     return t * t * (1.0 + t) / (1.0 + t + t * t * (1.0 / 3.0));
   }
   static __device__ __forceinline__ double lscale(double sl, double l) { return sl / (3.0 * l); }
+  static __device__ __forceinline__ double h(double q, double c) {
+    const double t = q * c;
+    return (5.0 / 3.0) * ((1.0 + t) * exp(-t));
+  }
 };
 
 #endif

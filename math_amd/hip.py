@@ -122,6 +122,10 @@ _SIGS = {
     "smg_cholesky_fwd_gp_mark_winv": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "smg_cholesky_fwd_gp_mark_stream": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
     "smg_gp_cov_inverse_adjoint_x": (_I, [_P, _I, _P, _I, _I, _P, _I, _L, _D, _P, _I, _D, _D, _P, _P]),
+    # per-dimension length scales (ARD): l is a host array of D doubles
+    "smg_gp_ard_scale": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "smg_gp_ard_cov_rev": (_I, [_P, _I, _P, _I, _I, _D, _P, _P, _I, _P]),
+    "smg_gp_ard_cov_inverse_adjoint": (_I, [_P, _I, _P, _I, _I, _P, _I, _L, _D, _P, _I, _D, _P, _P, _P]),
     "smg_log_sum_exp_fwd": (_I, [_P, _P, _L, _P]),
     "smg_log_sum_exp_rev": (_I, [_P, _P, _L, _D, _D, _P]),
     "smg_lgamma_fwd": (_I, [_P, _P, _L, _P]),

@@ -14,6 +14,7 @@
 #include <stan/math/rev/meta/operands_and_partials.hpp>
 #include <stan/math/rev/fun/gp_exp_quad_cov.hpp>
 #include <stan/math/rev/fun/gp_matern_cov.hpp>
+#include <stan/math/rev/fun/gp_ard_cov.hpp>
 #include <stan/math/rev/fun/cholesky_decompose.hpp>
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/multiply.hpp>
