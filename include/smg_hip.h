@@ -147,6 +147,13 @@ int smg_inv_block_fused(smg_ctx* ctx, int n);
  *         of 64, k of 32; even leading dimensions; 16-byte aligned A, B, C;
  *         C aliasing no operand), whatever its tile count */
 int smg_set_gemm_stage_mode(smg_ctx* ctx, int mode);
+/* dev / test hook: mode 1 (the default), the offset triangular K cuts of
+ * smg_gemm_cut and of the progressive K^{-1}'s products apply, and the tiles
+ * they shorten are spread over the XCDs; mode 0, every product ignores them
+ * and multiplies the stored zeros (one build compared with itself); mode 2,
+ * the cuts apply in the uncut product's tile placement.  The results of the
+ * three modes are the same numbers. */
+int smg_set_gemm_cut_mode(smg_ctx* ctx, int mode);
 
 /* ------------------------------------------------------- instrumentation ---
  * HIP-event timing of the kernel families on the context stream (used by
@@ -199,6 +206,18 @@ int smg_gemm_tri(smg_ctx* ctx, int transA, int transB, int uplo, int tri, int m,
  * region of an accumulated product.  bz must be a multiple of 128. */
 int smg_gemm_bz(smg_ctx* ctx, int transA, int transB, int uplo, int tri, int m, int n, int k, double alpha,
                 const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc, int bz);
+/* smg_gemm_bz (bz = 0: none) for operands with an offset triangle of stored
+ * zeros, as a block row [X | T] of a lower triangular matrix has with T its
+ * diagonal block at column cut:
+ *   cut_a >= 0: op(A)(i, t) = 0 for t < i - cut_a in the rows i >= cut_a,
+ *   cut_b >= 0: op(B)(t, j) = 0 for t < j - cut_b in the columns j >= cut_b,
+ *   -1: none.
+ * Every output tile skips the K range that the declared zeros of its rows and
+ * columns cover (not read); the tile order and the kernel are tri's and the
+ * uncut product's.  The progressive K^{-1}'s shares and Y parts use it. */
+int smg_gemm_cut(smg_ctx* ctx, int transA, int transB, int uplo, int tri, int m, int n, int k, double alpha,
+                 const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc, int bz,
+                 int cut_a, int cut_b);
 
 /* ---------------------------------------------------------- functors ---- */
 

@@ -434,11 +434,16 @@ int smg_inv_prog_init(smg_ctx* ctx, int n, double* ws) {
 }
 
 // the accumulated products of the parts: beta = 1 before the boundary bz
-// (rows bz > 0 / columns -bz < 0), 0 from it on; k = 0 has no earlier terms
+// (rows bz > 0 / columns -bz < 0), 0 from it on; k = 0 has no earlier terms.
+// The operand that holds W_k = [W_{k,0:r0} | W_kk] has W_kk's stored zeros
+// above its diagonal: the tiles of those rows (cut_a, the share's op(A) =
+// W_k^T) or columns (cut_b, the Y parts' op(B) = W_k) skip the K range that
+// the zero 64-blocks cover (smg_gemm_cut_impl) -- at n = 4096 7.3 of the 72.5
+// GFLOP the products executed.
 static int prog_acc(smg_ctx* ctx, int ta, int uplo, int m, int nc, int kk, const double* A, int lda,
-                    const double* B, int ldb, double* C, int ldc, int bz, bool first) {
-  if (first) return smg_gemm_impl(ctx, ta, 0, uplo, m, nc, kk, 1.0, A, lda, B, ldb, 0.0, C, ldc);
-  return smg_gemm_bz_impl(ctx, ta, 0, uplo, m, nc, kk, 1.0, A, lda, B, ldb, 1.0, C, ldc, 0, bz);
+                    const double* B, int ldb, double* C, int ldc, int bz, bool first, int cut_a, int cut_b) {
+  return smg_gemm_cut_impl(ctx, ta, 0, uplo, m, nc, kk, 1.0, A, lda, B, ldb, first ? 0.0 : 1.0, C, ldc, 0,
+                           first ? 0 : bz, cut_a, cut_b);
 }
 
 int smg_inv_prog_row(smg_ctx* ctx, const double* L, int ldl, double* aux, int n, double* ws, int k, int part,
@@ -466,29 +471,35 @@ int smg_inv_prog_row(smg_ctx* ctx, const double* L, int ldl, double* aux, int n,
       if (k == 0) return SMG_OK;
       return smg_gemm_impl(ctx, 0, 0, 0, P, r0, P, -1.0, Wkk, n, Y + r0, n, 0.0, W + r0, n, SMG_TRI_A_LOWER);
     case 2:  // C (lower, leading r1 x r1) += W_k^T W_k (rows r0.. first written here)
-      return prog_acc(ctx, 1, 1, r1, r1, P, W + r0, n, W + r0, n, C, n, r0, k == 0);
+      return prog_acc(ctx, 1, 1, r1, r1, P, W + r0, n, W + r0, n, C, n, r0, k == 0, r0, -1);
     case 3:  // Y_{k+1}[:, 0:r1] (+)= L_{k+1,k} W_{k,0:r1}
       if (r1 >= n) return SMG_OK;
-      return prog_acc(ctx, 0, 0, P, r1, P, L + r1 + (size_t)r0 * ldl, ldl, W + r0, n, Y + r1, n, -r0, k == 0);
+      return prog_acc(ctx, 0, 0, P, r1, P, L + r1 + (size_t)r0 * ldl, ldl, W + r0, n, Y + r1, n, -r0, k == 0, -1, r0);
     default:  // Y_{k+2:}[:, 0:r1] (+)= L_{k+2:,k} W_{k,0:r1}
       if (r1 + P >= n) return SMG_OK;
       return prog_acc(ctx, 0, 0, n - r1 - P, r1, P, L + r1 + P + (size_t)r0 * ldl, ldl, W + r0, n, Y + r1 + P, n, -r0,
-                      k == 0);
+                      k == 0, -1, r0);
   }
 }
 
 // device time of part `part` of block row k, us: flops at the rate these
 // products reach beside the panels (~30 TF/s; tools/ubench_gemm's shapes
-// run at 33-46 alone) plus ~6 us per launch
+// run at 33-46 alone) plus ~6 us per launch.  Parts 2 to 4 without what
+// their K cuts at W_kk's zero 64-blocks skip (prog_acc): tile row q of the
+// share's rows r0.. skips 64 q of K in its r0 / 64 + q + 1 tiles, tile column
+// c of the Y parts' columns r0.. skips 64 c in every row.
 double smg_inv_prog_cost(int n, int k, int part, bool inverses_here) {
   constexpr double P = SMG_NBR, rate = 30e6;  // flop per us
+  constexpr double T = 64.0, ycut = P * (P - T);  // (2 x 64 x sum_c 64 c) per row of a Y part
   const double r0 = k * P, r1 = r0 + P;
+  double scut = 0.0;
+  for (int q = 1; q < SMG_NBR / 64; ++q) scut += 2.0 * T * (T * q) * (r0 + T * (q + 1));
   switch (part) {
     case 0: return inverses_here ? 60.0 : 6.0;
     case 1: return k == 0 ? 0.0 : 6.0 + P * r0 * P / rate;
-    case 2: return 6.0 + r1 * r1 * P / rate;
-    case 3: return r1 >= n ? 0.0 : 6.0 + 2.0 * P * r1 * P / rate;
-    default: return r1 + P >= n ? 0.0 : 6.0 + 2.0 * (n - r1 - P) * r1 * P / rate;
+    case 2: return 6.0 + (r1 * r1 * P - scut) / rate;
+    case 3: return r1 >= n ? 0.0 : 6.0 + (2.0 * P * r1 * P - P * ycut) / rate;
+    default: return r1 + P >= n ? 0.0 : 6.0 + (n - r1 - P) * (2.0 * r1 * P - ycut) / rate;
   }
 }
 

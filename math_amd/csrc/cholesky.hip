@@ -25,6 +25,12 @@
 #include <cstdlib>
 #include <vector>
 
+// share of chol_fwd's slack estimate that the progressive K^{-1}'s parts are
+// queued against (builds for A/B runs override it)
+#ifndef SMG_PROG_SLACK_SCALE
+#define SMG_PROG_SLACK_SCALE 0.5
+#endif
+
 namespace {
 
 // one 64 x 64 tile pair per workgroup: tile (bi, bj) of the lower triangle
@@ -2027,7 +2033,7 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       // the block-row inverses became one launch, the full estimate measures slower
       // (same-box A/Bs of the scale, r05y / r05z2 / r05z3: 0.5 380.5 and 379.9, 0.65 379.0, 1.0 374.8
       // and 376.0, 0.4 371, 0.25 373.6, 0 370.6 evals/s)
-      if ((rc = queue_parts(J / NB2, 0.5 * slack))) return rc;
+      if ((rc = queue_parts(J / NB2, SMG_PROG_SLACK_SCALE * slack))) return rc;
     }
   }
   if (prog) {  // the rest of the rows but the last

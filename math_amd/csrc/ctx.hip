@@ -273,6 +273,7 @@ int smg_ctx_create(int device, size_t initial, smg_ctx** out) {
   ctx->inv_per_cu = ctx->inv_cus = -1;
   ctx->inv_mode = 0;
   ctx->gemm_stage = 0;
+  ctx->gemm_cut = SMG_GEMM_CUT_DEFAULT;
   ctx->host_scratch_size = 1u << 20;
   if (hipHostMalloc(&ctx->host_scratch, ctx->host_scratch_size, hipHostMallocDefault) != hipSuccess) {
     delete ctx;
@@ -687,6 +688,12 @@ int smg_set_inv_block_mode(smg_ctx* ctx, int mode) {
 int smg_set_gemm_stage_mode(smg_ctx* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 2) return SMG_ERR_ARG;
   ctx->gemm_stage = mode;
+  return SMG_OK;
+}
+
+int smg_set_gemm_cut_mode(smg_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return SMG_ERR_ARG;
+  ctx->gemm_cut = mode;
   return SMG_OK;
 }
 

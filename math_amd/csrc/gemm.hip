@@ -20,6 +20,10 @@
 // K stages of 32 in two LDS buffers (8 waves) or of 16 in three (4 waves).
 // Split-K writes fixed-order partial slabs reduced by a second kernel, so the
 // result is bitwise deterministic run to run.
+// Every tile's K range is cut to where its operands can be nonzero: whole
+// triangular operands (tri, which also sets the tile order) and offset
+// triangles in the last rows of op(A) / columns of op(B) (cut_a / cut_b, which
+// leave the order alone and only spread the shortened tiles over the XCDs).
 #include "smg_internal.h"
 #include <cstdio>
 #include <cstdlib>
@@ -241,7 +245,8 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
     int m, int n, int k, double alpha, const double* __restrict__ A, int lda,
     const double* __restrict__ B, int ldb, double beta, double* __restrict__ C,
     int ldc, int tiles_m, int ntiles, int kchunk, double* __restrict__ slab, long long sA,
-    long long sB, long long sC, int px, int ntp, int tri, double* __restrict__ C2, int ldc2, int bz) {
+    long long sB, long long sC, int px, int ntp, int tri, double* __restrict__ C2, int ldc2, int bz, int cut_a,
+    int cut_b, int cut_spread) {
   constexpr bool LOWT = MODE == 1 || MODE == 3;  // lower-triangle tiles
   constexpr bool UPT = MODE == 2;
   constexpr bool TRIC = LOWT || UPT;
@@ -292,8 +297,15 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
     const int r0 = rx * tiles_m / px, r1 = (rx + 1) * tiles_m / px;
     const int c0 = ry * tiles_n / py, c1 = (ry + 1) * tiles_n / py;
     const int rm = r1 - r0;
-    if (rm <= 0 || l >= rm * (c1 - c0)) return;
-    tile = (r0 + l % rm) + (c0 + l / rm) * tiles_m;
+    // cut_b: the tile columns from the cut on run ever shorter K ranges, and
+    // they are the last ones: in contiguous column ranges the XCDs of the
+    // last range(s) idle while the others set the kernel's time.  The columns
+    // are dealt round-robin instead (XCD column slot ry takes ry, ry + py,
+    // ...): as many column panels of B per XCD as before, the short ones last.
+    const bool deal = cut_spread && cut_b >= 0;
+    const int nc = deal ? (tiles_n - ry + py - 1) / py : c1 - c0;
+    if (rm <= 0 || l >= rm * nc) return;
+    tile = (r0 + l % rm) + (deal ? ry + py * (l / rm) : c0 + l / rm) * tiles_m;
   } else {
     tile = blockIdx.x % ntiles;
     split = blockIdx.x / ntiles;
@@ -330,8 +342,20 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
       // its L2 holds a few row panels of A and column panels of B at a time
       // (row-major over all XCDs, the last K^{-1} share fetched 530 MB
       // against 151 MB algorithmic, r06 PMC)
-      const int b = tile, x = b & 7, per = ntiles >> 3, extra = ntiles & 7;
-      tri_decode_grouped(x * per + (x < extra ? x : extra) + (b >> 3), tiles_m, bi, bj);
+      // (cut_a: the tile rows from the cut on run ever shorter K ranges and
+      // come last in that order, all in the last XCDs' runs, which then idle
+      // while the others set the kernel's time.  The order is split at the
+      // first row group that reaches the cut -- nu tiles before it, a multiple
+      // of 8 -- and every XCD takes a run of each part, the short tiles last.)
+      const int b = tile, x = b & 7, l = b >> 3;
+      int nu = 0;
+      if (cut_spread && cut_a >= 0) {
+        const int g0 = min((cut_a + BM - 1) / BM, T) / 8 * 8;
+        nu = (g0 * (g0 + 1) / 2) & ~7;
+      }
+      const int rest = ntiles - nu, per = rest >> 3, extra = rest & 7;
+      const int t = l < (nu >> 3) ? x * (nu >> 3) + l : nu + x * per + (x < extra ? x : extra) + l - (nu >> 3);
+      tri_decode_grouped(t, tiles_m, bi, bj);
     } else {
       tri_decode(tile, bi, bj);
     }
@@ -354,7 +378,7 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
   const int i0 = bi * BM, j0 = bj * BN;
   int kbeg = split * kchunk;
   int kend = min(k, kbeg + kchunk);
-  if (tri) {
+  if (tri || cut_a >= 0 || cut_b >= 0) {
     // triangular operands: only k where both op(A)(i, k) and op(B)(k, j) can
     // be nonzero for some (i, j) of this tile (BK-aligned: the extra
     // elements are stored zeros)
@@ -363,6 +387,12 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
     if (tri & 2) lo = max(lo, i0);       // op(A) upper: zero for k < i
     if (tri & 4) lo = max(lo, j0);       // op(B) lower: zero for k < j
     if (tri & 8) hi = min(hi, j0 + BN);  // op(B) upper: zero for k > j
+    // offset triangles (no say in the tile order, unlike tri): op(A)(i, k) = 0
+    // for k < i - cut_a in the rows i >= cut_a, op(B)(k, j) = 0 for
+    // k < j - cut_b in the columns j >= cut_b (a block row [X | T] of a lower
+    // triangular matrix, T its diagonal block: T's tile band starts at the cut)
+    if (cut_a >= 0 && i0 >= cut_a) lo = max(lo, i0 - cut_a);
+    if (cut_b >= 0 && j0 >= cut_b) lo = max(lo, j0 - cut_b);
     lo = lo / BK * BK;
     kbeg = max(kbeg, lo);
     kend = min(kend, hi);
@@ -649,6 +679,35 @@ thread_local double* t_c2 = nullptr;
 thread_local int t_ldc2 = 0;
 // the beta-zero boundary of the next product (k_gemm's bz; smg_gemm_bz_impl)
 thread_local int t_bz = 0;
+// the offset triangular K cuts of the next product (k_gemm's cut_a / cut_b,
+// -1: none; smg_gemm_cut_impl)
+thread_local int t_cut_a = -1, t_cut_b = -1;
+
+// Multiply-adds x 2 that the offset cuts take off a product without triangular
+// operands, tile by tile as k_gemm skips them; a triangle of C counted by its
+// elements, as smg_gemm_impl counts the uncut product.
+template <int BM, int BN, int BK>
+double cut_flops(int mode, int m, int n, int k, int cut_a, int cut_b) {
+  double f = 0.0;
+  for (int j0 = 0; j0 < n; j0 += BN)
+    for (int i0 = 0; i0 < m; i0 += BM) {
+      int lo = 0;
+      if (cut_a >= 0 && i0 >= cut_a) lo = i0 - cut_a;
+      if (cut_b >= 0 && j0 >= cut_b && j0 - cut_b > lo) lo = j0 - cut_b;
+      lo = lo / BK * BK;
+      if (lo > k) lo = k;
+      if (lo == 0) continue;
+      const int i1 = i0 + BM < m ? i0 + BM : m, j1 = j0 + BN < n ? j0 + BN : n;
+      double el = 0.0;
+      for (int j = j0; j < j1; ++j) {
+        const int a = (mode == 1 || mode == 3) && j > i0 ? j : i0;  // lower: rows i >= j
+        const int b = mode == 2 && j + 1 < i1 ? j + 1 : i1;         // upper: rows i <= j
+        if (b > a) el += b - a;
+      }
+      f += 2.0 * lo * el;
+    }
+  return f;
+}
 
 template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1, int NB = 0>
 int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
@@ -657,6 +716,12 @@ int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
   constexpr bool TRIC = MODE == 1 || MODE == 2 || MODE == 3;
   const int tm = smg_ceil_div(m, BM), tn = smg_ceil_div(n, BN);
   const int ntiles = (TRIC && m == n && BM == BN) ? tm * (tm + 1) / 2 : tm * tn;
+  // (ctx->gemm_cut 0: every product ignores its offset cuts; 2: it takes them
+  // in the uncut product's tile placement, smg_set_gemm_cut_mode)
+  const int cut_a = ctx->gemm_cut ? t_cut_a : -1, cut_b = ctx->gemm_cut ? t_cut_b : -1;
+  const int cut_spread = ctx->gemm_cut == 1;
+  if (ctx->prof_on && !tri && (cut_a >= 0 || cut_b >= 0))
+    ctx->prof_flops[SMG_FAM_GEMM] -= batch * cut_flops<BM, BN, BK>(MODE, m, n, k, cut_a, cut_b);
   // split K when the tile grid cannot fill the 256 CUs and K is long
   int splits = 1;
   const int target = 512;
@@ -713,7 +778,7 @@ int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
   hipLaunchKernelGGL((k_gemm<BM, BN, BK, TA, TB, MODE, KS, NB>), dim3(ntp * splits, batch), dim3(256 * KS), 0,
                      ctx->stream, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tm,
                      ntiles, kchunk, slab, sA, sB, sC, px, ntp, tri, MODE >= 3 ? t_c2 : nullptr,
-                     MODE >= 3 ? t_ldc2 : 0, t_bz);
+                     MODE >= 3 ? t_ldc2 : 0, t_bz, cut_a, cut_b, cut_spread);
   if (splits > 1) {
     const long long tot = (long long)m * n;
     if ((m & 1) == 0) {
@@ -934,10 +999,24 @@ int smg_gemm_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k,
 // multiple of 128 (every tile lies on one side of it).
 int smg_gemm_bz_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k, double alpha, const double* A,
                      int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri, int bz) {
-  if (bz % 128) return SMG_ERR_ARG;
+  return smg_gemm_cut_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, bz, -1, -1);
+}
+
+// smg_gemm_bz_impl (bz = 0: none) for operands with an offset triangle of
+// stored zeros, whose K range every tile skips (-1: no such triangle):
+//   cut_a >= 0: op(A)(i, t) = 0 for t < i - cut_a in the rows i >= cut_a,
+//   cut_b >= 0: op(B)(t, j) = 0 for t < j - cut_b in the columns j >= cut_b.
+// The tile order, the kernel and its staging are chosen as without the cuts.
+int smg_gemm_cut_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k, double alpha, const double* A,
+                      int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri, int bz, int cut_a,
+                      int cut_b) {
+  if (bz % 128 || cut_a < -1 || cut_b < -1) return SMG_ERR_ARG;
   t_bz = bz;
+  t_cut_a = cut_a;
+  t_cut_b = cut_b;
   const int rc = smg_gemm_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
   t_bz = 0;
+  t_cut_a = t_cut_b = -1;
   return rc;
 }
 
@@ -1002,6 +1081,14 @@ extern "C" int smg_gemm_bz(smg_ctx* ctx, int ta, int tb, int uplo, int tri, int 
   if (!ctx || m <= 0 || n <= 0 || k <= 0 || tri < 0 || tri > 15 || alpha == 0.0) return SMG_ERR_ARG;
   if (!A || !B || !C || ldc < m || lda < (ta ? k : m) || ldb < (tb ? n : k)) return SMG_ERR_ARG;
   return smg_gemm_bz_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, bz);
+}
+
+extern "C" int smg_gemm_cut(smg_ctx* ctx, int ta, int tb, int uplo, int tri, int m, int n, int k, double alpha,
+                            const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc,
+                            int bz, int cut_a, int cut_b) {
+  if (!ctx || m <= 0 || n <= 0 || k <= 0 || tri < 0 || tri > 15 || alpha == 0.0) return SMG_ERR_ARG;
+  if (!A || !B || !C || ldc < m || lda < (ta ? k : m) || ldb < (tb ? n : k)) return SMG_ERR_ARG;
+  return smg_gemm_cut_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, bz, cut_a, cut_b);
 }
 
 extern "C" int smg_gemm(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k,

@@ -9,6 +9,11 @@
 
 #include "../../include/smg_hip.h"
 
+// a new context's smg_set_gemm_cut_mode (builds for A/B runs override it)
+#ifndef SMG_GEMM_CUT_DEFAULT
+#define SMG_GEMM_CUT_DEFAULT 1
+#endif
+
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
 
@@ -90,6 +95,7 @@ struct smg_ctx {
   int inv_per_cu, inv_cus;  // k_inv_block512's occupancy per CU and the CUs (-1: not yet queried)
   int inv_mode;      // 1: the block inverses by the six-launch chain (smg_set_inv_block_mode, a test hook)
   int gemm_stage;    // the 64 x 64 GEMM tile's staging: 0 policy, 1 registers, 2 LDS-DMA where eligible (smg_set_gemm_stage_mode)
+  int gemm_cut;      // the GEMMs' offset triangular K cuts: 1 applied, 0 ignored, 2 applied in the uncut tile placement (smg_set_gemm_cut_mode)
   // pinned host scratch
   void* host_scratch;
   size_t host_scratch_size;
@@ -243,6 +249,12 @@ int smg_gemm_impl(smg_ctx* ctx, int transA, int transB, int uplo, int m, int n,
 // the same with beta taken as 0 from row bz (bz > 0) / column -bz (bz < 0) of C on
 int smg_gemm_bz_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k, double alpha, const double* A,
                      int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri, int bz);
+// the same (bz = 0: none) with offset triangular K cuts: op(A)(i, t) = 0 for
+// t < i - cut_a in the rows i >= cut_a, op(B)(t, j) = 0 for t < j - cut_b in
+// the columns j >= cut_b (stored zeros; -1: none).  The tile order stays tri's.
+int smg_gemm_cut_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k, double alpha, const double* A,
+                      int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri, int bz, int cut_a,
+                      int cut_b);
 
 // C = alpha op(A) op(B) + beta C and C2 = tril(C) with halved diagonal (one pass)
 int smg_gemm_dual_impl(smg_ctx* ctx, int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda,

@@ -51,6 +51,7 @@ _SIGS = {
     "smg_set_inv_block_mode": (_I, [_P, _I]),
     "smg_inv_block_fused": (_I, [_P, _I]),
     "smg_set_gemm_stage_mode": (_I, [_P, _I]),
+    "smg_set_gemm_cut_mode": (_I, [_P, _I]),
     "smg_pinned_io": (_P, [_P, _S]),
     "smg_pinned_result": (_P, [_P, _S]),
     "smg_gather_scalars": (_I, [_P, _P, _I, _P, _P]),
@@ -65,6 +66,7 @@ _SIGS = {
     "smg_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _D, _P, _I, _P, _I, _D, _P, _I]),
     "smg_gemm_tri": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I, _P, _I, _D, _P, _I]),
     "smg_gemm_bz": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I, _P, _I, _D, _P, _I, _I]),
+    "smg_gemm_cut": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I, _P, _I, _D, _P, _I, _I, _I, _I]),
     "smg_gp_exp_quad_cov_fwd": (_I, [_P, _P, _I, _D, _D, _P, _I]),
     "smg_gp_exp_quad_cov_rev": (_I, [_P, _P, _I, _D, _D, _P, _I, _P]),
     "smg_bernoulli_logit_glm_checked": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P]),

@@ -1,6 +1,6 @@
 // Dev microbenchmark: smg_gemm on the shapes of one blocked-Cholesky step
 // (tools/ubench_shapes.h) plus an empty-kernel floor.
-// usage: ubench_gemm [shape index | -1 [stage mode (smg_set_gemm_stage_mode)]]
+// usage: ubench_gemm [shape index | -1 [stage mode (smg_set_gemm_stage_mode) [cut mode (smg_set_gemm_cut_mode)]]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +16,7 @@ int main(int argc, char** argv) {
   smg_ctx_create(0, 1ull << 30, &ctx);
   hipStream_t s = (hipStream_t)smg_ctx_stream(ctx);
   if (argc > 2 && smg_set_gemm_stage_mode(ctx, atoi(argv[2]))) return 1;
+  if (argc > 3 && smg_set_gemm_cut_mode(ctx, atoi(argv[3]))) return 1;
   const int n = 4096;
   double *A, *B, *C;
   hipMalloc(&A, sizeof(double) * n * n);
@@ -42,17 +43,19 @@ int main(int argc, char** argv) {
     if (only >= 0 && int(si) != only) continue;
     const int lda = n, ldb = n, ldc = n;
     for (int w = 0; w < 3; ++w)
-      smg_gemm_tri(ctx, sh.ta, sh.tb, sh.uplo, sh.tri, sh.m, sh.n, sh.k, -1e-3, A, lda, B, ldb, 1.0, C, ldc);
+      smg_gemm_cut(ctx, sh.ta, sh.tb, sh.uplo, sh.tri, sh.m, sh.n, sh.k, -1e-3, A, lda, B, ldb, 1.0, C, ldc, 0, sh.cut_a,
+                   sh.cut_b);
     const int rr = sh.k == 4096 ? 5 : reps;
     hipEventRecord(e0, s);
     for (int r = 0; r < rr; ++r)
-      smg_gemm_tri(ctx, sh.ta, sh.tb, sh.uplo, sh.tri, sh.m, sh.n, sh.k, -1e-3, A, lda, B, ldb, 1.0, C, ldc);
+      smg_gemm_cut(ctx, sh.ta, sh.tb, sh.uplo, sh.tri, sh.m, sh.n, sh.k, -1e-3, A, lda, B, ldb, 1.0, C, ldc, 0, sh.cut_a,
+                   sh.cut_b);
     hipEventRecord(e1, s);
     hipEventSynchronize(e1);
     hipEventElapsedTime(&ms, e0, e1);
     const double us = ms * 1000 / rr;
     const double fl = ub_flops(sh);
-    printf("%-34s %8.2f us  %6.2f TF/s  \n", sh.name, us, fl / us * 1e-6);
+    printf("%-48s %8.2f us  %6.2f TF/s  \n", sh.name, us, fl / us * 1e-6);
   }
   smg_ctx_destroy(ctx);
 }

@@ -8,6 +8,7 @@ struct ub_shape {
   int ta, tb, uplo, m, n, k;
   int tri;  // SMG_TRI_* (smg_gemm_tri), 0: dense
   double fl;  // useful flops when the formula below does not apply (0: use it)
+  int cut_a = -1, cut_b = -1;  // offset triangular K cuts (smg_gemm_cut), -1: none
 };
 static const ub_shape ub_shapes[] = {
     // forward: (a) next panel's columns (lower trapezoid), (b) the rest (SYRK)
@@ -41,6 +42,12 @@ static const ub_shape ub_shapes[] = {
     {"prog Y NN triB (512,3584,3584)", 0, 0, 0, 512, 3584, 3584, 4},
     {"prog Y NN dense (512,3584,3584)", 0, 0, 0, 512, 3584, 3584},
     {"prog W NN triA (512,3584,512)", 0, 0, 0, 512, 3584, 512, 1},
+    // the same with the K cut at W_kk's zero 64-blocks (flops: the uncut count
+    // minus 2 x 64^3 per skipped slab; ubench_gemm's third argument is
+    // smg_set_gemm_cut_mode, 0 = uncut)
+    {"prog share TN lower cut_a 3584 (4096,4096,512)", 1, 0, 1, 4096, 4096, 512, 0, 7.682e9, 3584, -1},
+    {"prog Y NN cut_b 3072 (512,3584,512)", 0, 0, 0, 512, 3584, 512, 0, 1.7616e9, -1, 3072},
+    {"prog Y NN cut_b 1536 (2048,2048,512)", 0, 0, 0, 2048, 2048, 512, 0, 3.825e9, -1, 1536},
     // the HVP's Cholesky tangent node at N = 4096 (chol_tangent.hip); flops
     // counted over the cut K ranges (N^3 = 68.7 GFLOP)
     {"hvp T=tril(W A') NT lower triA", 0, 1, 1, 4096, 4096, 4096, 1, 2.0 / 3.0 * 68719476736.0},
