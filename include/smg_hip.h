@@ -385,8 +385,11 @@ int smg_log_determinant_rev(smg_ctx* ctx, const double* LU, const int* piv,
  * row 4; mix/fvar_functors.hpp):
  *   smg_add_tril: Y(i >= j) += alpha X(i >= j) (m x n).
  *   smg_lse_tangent_fwd: out[0] = log_sum_exp(x), out[1] = sum_i
- *     exp(x_i - out[0]) xd_i (fwd/mat/fun/log_sum_exp.hpp).  rev: xadj +=
- *     adj p (xd - t), xdadj += adj p, p = exp(x - lse) (either may be NULL).
+ *     exp(x_i - out[0]) xd_i (fwd/mat/fun/log_sum_exp.hpp).  With an x_i at
+ *     +inf out[0] = +inf, as smg_log_sum_exp_fwd, and out[1] = the mean of xd
+ *     over the entries at +inf (the softmax's limit); n == 0 or every x_i at
+ *     -inf: out = [-inf, 0].  rev: xadj += adj p (xd - t), xdadj += adj p,
+ *     p = exp(x - lse) (either may be NULL).
  *   smg_glm_tangent_fwd: out[0] = sum_i d_i (etad_i + alphad), d_i = the
  *     reference's theta_derivative of bernoulli_logit_glm_lpmf at theta_i =
  *     eta_i + alpha (prim/mat/prob/bernoulli_logit_glm_lpmf.hpp:117-123).
@@ -454,7 +457,7 @@ int smg_multiply_lower_fwd(smg_ctx* ctx, const double* L, int ldl, const double*
  * prim/mat/fun/cholesky_decompose.hpp).  aux: smg_cholesky_fwd's block
  * inverses of L (NULL: rebuilt).  fwd: W = L^{-1} (lower, zeros
  * above), Wt = W^T, Y = W A' W^T (symmetric, full), P = Phi(Y) (its strict
- * upper zeroed only inside the diagonal tiles: the node's own products read
+ * upper zeroed only inside the diagonal 64 x 64 blocks: the node's own products read
  * no other part of it), Ld = L P (lower); W, Wt, Y, P: n x n, ld.  rev
  * (Ld_adj lower): Ladj += tril(Ld_adj P^T) - tril(W^T S Y), A'adj +=
  * (1/2) W^T S W (symmetric, both triangles), with S = Phi(Padj) + Phi(Padj)^T,

@@ -29,7 +29,8 @@ namespace {
 
 // W[lo:hi, lo:hi] = L[lo:hi, lo:hi]^{-1} from the 512-row block inverses
 // (aux level SMG_AUX_W512, ld n): halves combined by
-//   W21 = -W22 (L21 W11)      (T: a (hi-mid) x (mid-lo) workspace, ld n)
+//   W21 = -W22 (L21 W11)      (T: a (hi-mid) x (mid-lo) workspace, ld ldw: the
+//                               caller's Y, whose rows from n on are not written)
 int inv_rec(smg_ctx* ctx, const double* L, int ldl, const double* w512, int n, double* W, int ldw, double* T, int lo,
             int hi) {
   if (hi - lo == SMG_NBR)
@@ -40,9 +41,9 @@ int inv_rec(smg_ctx* ctx, const double* L, int ldl, const double* w512, int n, d
   if (rc) return rc;
   const int a = hi - mid, b = mid - lo;
   rc = smg_gemm_impl(ctx, 0, 0, 0, a, b, b, 1.0, L + mid + (size_t)lo * ldl, ldl, W + lo + (size_t)lo * ldw, ldw,
-                     0.0, T, n, SMG_TRI_B_LOWER);
+                     0.0, T, ldw, SMG_TRI_B_LOWER);
   if (rc) return rc;
-  return smg_gemm_impl(ctx, 0, 0, 0, a, b, a, -1.0, W + mid + (size_t)mid * ldw, ldw, T, n, 0.0,
+  return smg_gemm_impl(ctx, 0, 0, 0, a, b, a, -1.0, W + mid + (size_t)mid * ldw, ldw, T, ldw, 0.0,
                        W + mid + (size_t)lo * ldw, ldw, SMG_TRI_A_LOWER);
 }
 
@@ -73,8 +74,10 @@ int smg_chol_tangent_fwd(smg_ctx* ctx, const double* L, int ldl, const double* a
   if (n == 0) return SMG_OK;
   if (!L || !Ad || !W || !Wt || !Y || !P || !Ld || ldl < n || ldad < n || ld < n) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_TRSV);
-  // W = L^{-1} (lower, stored zeros above)
-  int rc = smg_memset(ctx, W, 0, sizeof(double) * (size_t)ld * n);
+  // W = L^{-1} (lower, stored zeros above): its n x n entries cleared column
+  // by column, one memset where they are contiguous (the rows from n to ld
+  // and what follows the last column are not W's)
+  int rc = ld == n ? smg_memset(ctx, W, 0, sizeof(double) * (size_t)ld * n) : smg_scale_impl(ctx, n, n, 0.0, W, ld, 0);
   if (rc) return rc;
   if (n % SMG_NBR == 0 && n >= 2 * SMG_NBR) {
     const double* w = aux;  // the factorisation's block inverses, or rebuilt here
@@ -122,12 +125,18 @@ int smg_chol_tangent_fwd_w(smg_ctx* ctx, const double* L, int ldl, const double*
   // (A' is symmetric -- the tangent of the factorised symmetric matrix -- so
   // it enters as op(B) = A'^T: the B tile then loads n-contiguous runs; the
   // NN form with a k-contiguous B ran 30-50 % slower in the HVP's trace)
+  // (Ld's strict upper is cleared first, not after: the lower products below
+  // leave it alone, and Y's diagonal tiles multiply T's upper entries there by
+  // W's stored zeros -- what a recycled buffer holds may be NaN or Inf)
+  if ((rc = smg_scale_impl(ctx, n, n, 0.0, Ld, ld, 3))) return rc;
   if ((rc = smg_gemm_impl(ctx, 0, 1, 1, n, n, n, 1.0, W, ld, Ad, ldad, 0.0, Ld, ld, SMG_TRI_A_LOWER))) return rc;
   // (P = Phi(Y) from the same epilogue: its strict upper is zeroed inside the
   // diagonal 64-blocks only -- L P cuts K to k >= j, T P^T to k <= j, in whole
   // blocks, so no other upper entry is read)
   if ((rc = smg_gemm_sym_phi_impl(ctx, 0, 1, n, n, 1.0, Ld, ld, W, ld, 0.0, Y, ld, P, ld, SMG_TRI_B_UPPER))) return rc;
-  if ((rc = smg_multiply_lower_fwd(ctx, L, ldl, P, ld, n, Ld, ld))) return rc;
+  // L' = L P: smg_multiply_lower_fwd's product (its clear of the upper is the one above)
+  if ((rc = smg_gemm_impl(ctx, 0, 0, 1, n, n, n, 1.0, L, ldl, P, ld, 0.0, Ld, ld, SMG_TRI_A_LOWER | SMG_TRI_B_LOWER)))
+    return rc;
   return fork ? join_side(ctx, 1) : SMG_OK;
 }
 

@@ -616,6 +616,10 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
         C[i + (size_t)j * ldc] = out;
         if (MODE == 3 && i > j) C[j + (size_t)i * ldc] = out;
         if ((MODE == 4 || (MODE == 3 && C2)) && i >= j) C2[i + (size_t)j * ldc2] = i == j ? 0.5 * out : out;
+        // (Phi's zero upper covers the diagonal 64-blocks whatever the tile: a
+        // reader on 64 x 64 tiles cuts K to those.  A smaller tile below the
+        // diagonal of such a block clears its mirror, which no tile owns)
+        if (MODE == 3 && BM < 64 && C2 && i0 != j0 && (i >> 6) == (j >> 6)) C2[j + (size_t)i * ldc2] = 0.0;
       }
     }
     if (c0 + ECH < BN) __syncthreads();
@@ -1041,7 +1045,7 @@ int smg_gemm_dual_impl(smg_ctx* ctx, int ta, int tb, int m, int n, int k, double
 // C = alpha op(A) op(B) + beta C, symmetric: its lower triangle computed and
 // stored mirrored (uplo 3), and P = Phi(C) (strict lower, halved diagonal) as
 // a second output.  P's strict upper is written (zeros) only inside the
-// diagonal tiles: a reader must cut K to P's lower triangle
+// diagonal 64-blocks: a reader must cut K to P's lower triangle
 // (SMG_TRI_B_LOWER / TRI_B_UPPER on P^T), as the Cholesky tangent's do.
 int smg_gemm_sym_phi_impl(smg_ctx* ctx, int ta, int tb, int n, int k, double alpha, const double* A, int lda,
                           const double* B, int ldb, double beta, double* C, int ldc, double* P, int ldp, int tri) {

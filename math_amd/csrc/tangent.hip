@@ -102,7 +102,9 @@ __global__ __launch_bounds__(256) void k_copy_tril_col2(int m, int n, const doub
   }
 }
 
-// out = [lse(x), sum_i exp(x_i - lse) x'_i]
+// out = [lse(x), sum_i exp(x_i - lse) x'_i]; a maximum of +inf gives
+// out[0] = +inf, as smg_log_sum_exp_fwd (exp(inf - inf) is NaN), with the
+// softmax's weight shared equally by the entries at +inf
 __global__ __launch_bounds__(TT) void k_lse_tangent_fwd(const double* __restrict__ x, const double* __restrict__ xd,
                                                        long long n, double* __restrict__ out) {
   __shared__ double sh[TT / 64];
@@ -112,14 +114,14 @@ __global__ __launch_bounds__(TT) void k_lse_tangent_fwd(const double* __restrict
   double s = 0.0, u = 0.0;
   if (m > -INFINITY)
     for (long long i = threadIdx.x; i < n; i += TT) {
-      const double e = exp(x[i] - m);
+      const double e = m == INFINITY ? (x[i] == m ? 1.0 : 0.0) : exp(x[i] - m);
       s += e;
       u += e * xd[i];
     }
   s = block_sum(s, sh);
   u = block_sum(u, sh);
   if (threadIdx.x == 0) {
-    out[0] = m > -INFINITY ? m + log(s) : -INFINITY;
+    out[0] = m == INFINITY ? m : (m > -INFINITY ? m + log(s) : -INFINITY);
     out[1] = m > -INFINITY ? u / s : 0.0;
   }
 }

@@ -276,7 +276,8 @@ int smg_mdivide_left_tri_aux_rev(smg_ctx* ctx, int lower, const double* A, int l
                                  int ldaa, double* Badj, int ldba, double* ws) {
   if (!ctx || m < 0 || n < 0) return SMG_ERR_ARG;
   if (m == 0 || n == 0) return SMG_OK;
-  if (!A || !C || !Cadj || !ws) return SMG_ERR_ARG;
+  if (!A || !C || !Cadj || !ws || lda < m || ldc < m || ldca < m) return SMG_ERR_ARG;
+  if ((Aadj && ldaa < m) || (Badj && ldba < m)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_TRSV);
   // adjB = tri(A)^{-T} Cadj   (mdivide_left_tri.hpp:104-107)
   int rc;
