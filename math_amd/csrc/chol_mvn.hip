@@ -426,13 +426,7 @@ bool smg_inv_prog_ok(int n) { return n % SMG_NBR == 0 && n >= 2 * SMG_NBR; }
 // that row / column on (smg_gemm_bz_impl) and beta = 1 before it.  Zeroing
 // the 2 n^2 doubles instead put 268 MB of stores beside the first panel
 // (GP 356-362 -> 365-368 evals/s without it).
-int smg_inv_prog_init(smg_ctx* ctx, int n, double* ws) {
-  (void)ctx;
-  (void)n;
-  (void)ws;
-  return SMG_OK;
-}
-
+//
 // the accumulated products of the parts: beta = 1 before the boundary bz
 // (rows bz > 0 / columns -bz < 0), 0 from it on; k = 0 has no earlier terms.
 // The operand that holds W_k = [W_{k,0:r0} | W_kk] has W_kk's stored zeros
@@ -482,25 +476,18 @@ int smg_inv_prog_row(smg_ctx* ctx, const double* L, int ldl, double* aux, int n,
   }
 }
 
-// device time of part `part` of block row k, us: flops at the rate these
-// products reach beside the panels (~30 TF/s; tools/ubench_gemm's shapes
-// run at 33-46 alone) plus ~6 us per launch.  Parts 2 to 4 without what
-// their K cuts at W_kk's zero 64-blocks skip (prog_acc): tile row q of the
-// share's rows r0.. skips 64 q of K in its r0 / 64 + q + 1 tiles, tile column
-// c of the Y parts' columns r0.. skips 64 c in every row.
-double smg_inv_prog_cost(int n, int k, int part, bool inverses_here) {
+// device time of block row k's K^{-1} share (part 2), us: flops at the rate
+// these products reach beside the panels (~30 TF/s; tools/ubench_gemm's shapes
+// run at 33-46 alone) plus ~6 us per launch, without what its K cuts at
+// W_kk's zero 64-blocks skip (prog_acc): tile row q of the share's rows r0..
+// skips 64 q of K in its r0 / 64 + q + 1 tiles.
+double smg_inv_share_cost(int k) {
   constexpr double P = SMG_NBR, rate = 30e6;  // flop per us
-  constexpr double T = 64.0, ycut = P * (P - T);  // (2 x 64 x sum_c 64 c) per row of a Y part
+  constexpr double T = 64.0;
   const double r0 = k * P, r1 = r0 + P;
   double scut = 0.0;
   for (int q = 1; q < SMG_NBR / 64; ++q) scut += 2.0 * T * (T * q) * (r0 + T * (q + 1));
-  switch (part) {
-    case 0: return inverses_here ? 60.0 : 6.0;
-    case 1: return k == 0 ? 0.0 : 6.0 + P * r0 * P / rate;
-    case 2: return 6.0 + (r1 * r1 * P - scut) / rate;
-    case 3: return r1 >= n ? 0.0 : 6.0 + (2.0 * P * r1 * P - P * ycut) / rate;
-    default: return r1 + P >= n ? 0.0 : 6.0 + (n - r1 - P) * (2.0 * r1 * P - ycut) / rate;
-  }
+  return 6.0 + (r1 * r1 * P - scut) / rate;
 }
 
 extern "C" {
@@ -672,7 +659,7 @@ int smg_cholesky_inv_t_async(smg_ctx* ctx, const double* L, int ldl, const doubl
   SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->inv_ev_main, 0));
   int rc;
   {
-    smg_on_side on(ctx);  // V only: K^{-1} in the reverse (formed here it measured no faster)
+    smg_on_stream on(ctx, ctx->side);  // V only: K^{-1} in the reverse (formed here it measured no faster)
     rc = form_v(ctx, L, ldl, aux, n, ws, ws + (size_t)n * n);
   }
   if (rc) return rc;

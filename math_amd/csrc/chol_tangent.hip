@@ -113,7 +113,7 @@ int smg_chol_tangent_fwd_w(smg_ctx* ctx, const double* L, int ldl, const double*
   const bool fork = smg_side_begin(ctx) == SMG_OK;
   if (fork) {
     if ((rc = fork_side(ctx, 0))) return rc;
-    smg_on_side on(ctx);
+    smg_on_stream on(ctx, ctx->side);
     if ((rc = smg_transpose(ctx, n, n, W, ld, Wt, ld, 0.0))) return rc;
   } else if ((rc = smg_transpose(ctx, n, n, W, ld, Wt, ld, 0.0))) {
     return rc;
@@ -165,8 +165,7 @@ int smg_chol_tangent_rev(smg_ctx* ctx, const double* L, int ldl, const double* W
   const bool fork = Ladj && smg_side_begin(ctx) == SMG_OK;
   if (fork && (rc = fork_side(ctx, 2))) return rc;
   {
-    smg_on_side on(ctx);
-    if (!fork) ctx->stream = ctx->main_stream;
+    smg_on_stream on(ctx, fork ? ctx->side : ctx->stream);
     // (S = Padj's lower triangle mirrored: the product's symmetric store, uplo 3)
     if ((rc = smg_gemm_impl(ctx, 1, 0, 3, n, n, n, 1.0, L, ldl, M, n, 0.0, S, n, SMG_TRI_A_UPPER | SMG_TRI_B_LOWER)))
       return rc;
@@ -178,8 +177,7 @@ int smg_chol_tangent_rev(smg_ctx* ctx, const double* L, int ldl, const double* W
   if ((rc = smg_gemm_impl(ctx, 0, 0, 0, n, n, n, 1.0, Wt, ld, S, n, 0.0, M, n, SMG_TRI_A_UPPER))) return rc;
   if (Adadj) {
     if (fork && (rc = fork_side(ctx, 4))) return rc;
-    smg_on_side on(ctx);
-    if (!fork) ctx->stream = ctx->main_stream;
+    smg_on_stream on(ctx, fork ? ctx->side : ctx->stream);
     // (1/2) M W = (1/2) W^T S W is symmetric: its UPPER triangle is computed
     // (with op(B) = W lower, tile column j takes K = n - j over j + 1 tiles:
     // half the lower triangle's multiply-adds, N^3 / 6 instead of N^3 / 3) and

@@ -1554,7 +1554,7 @@ int chol_rev_two_level(smg_ctx* ctx, const double* L, int ldl, const double* aux
           SMG_HIP_TRY(hipEventRecord(E, ctx->stream));
           SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, E, 0));
           {
-            smg_on_side on(ctx);
+            smg_on_stream on(ctx, ctx->side);
             rc = smg_gemm_impl(ctx, 0, 0, 0, m, J, bs, -1.0, Cr, ldcr, L + J, ldl, 1.0, La + K, ldla);
             if (!rc && Cw) rc = smg_copy_impl(ctx, m, bs, Cw, m, Ca, ldla, 1.0, 0);
           }
@@ -1634,9 +1634,64 @@ struct chol_stream_sink {
   double* host;     // host (pinned), the same
   int marker_base;  // marker slot of panel 0
 };
-int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, double* Dinv,
-             bool check_sym, bool mark = false, double* inv_ws = nullptr, int* inv_started = nullptr,
-             const chol_stream_sink* sink = nullptr, bool w_only = false, const smg_gp_source* src = nullptr);
+
+// chol_fwd's arguments: the exported smg_cholesky_fwd* entries fill them in
+struct chol_fwd_args {
+  const double* A;           // the stored input, ld lda (src == NULL)
+  int lda;
+  const smg_gp_source* src;  // or the input described (A unused): generated into L in place of the copy
+  int n;
+  double* L;
+  int ldl;
+  double* Dinv;              // aux (NULL: a workspace)
+  bool check_sym, mark;      // the symmetric check; the status mark behind the last panel
+  double* inv_ws;            // progressive W = L^{-1} / K^{-1} (chol_mvn.hip) where the schedule allows it,
+  int* inv_started;          //   which *inv_started reports (required with inv_ws)
+  const chol_stream_sink* sink;
+  bool w_only;               // W alone: no K^{-1} shares
+};
+int chol_fwd(smg_ctx* ctx, const chol_fwd_args& a);
+
+chol_fwd_args fwd_stored(const double* A, int lda, int n, double* L, int ldl, double* Dinv, bool check_sym,
+                         bool mark) {
+  return {A, lda, nullptr, n, L, ldl, Dinv, check_sym, mark, nullptr, nullptr, nullptr, false};
+}
+chol_fwd_args fwd_described(const smg_gp_source* src, double* L, int ldl, double* Dinv) {  // src != NULL
+  return {nullptr, 0, src, src->n, L, ldl, Dinv, true, true, nullptr, nullptr, nullptr, false};
+}
+
+// the _inv (ws optional) and _winv (w_only: ws required) entries
+int fwd_with_inverse(smg_ctx* ctx, chol_fwd_args a, double* ws, int* started, bool w_only) {
+  if (!started) return SMG_ERR_ARG;
+  *started = 0;
+  if (w_only ? (!ws || !a.Dinv) : (ws && !a.Dinv)) return SMG_ERR_ARG;
+  a.inv_ws = ws;
+  a.inv_started = started;
+  a.w_only = w_only;
+  return chol_fwd(ctx, a);
+}
+
+// the _stream entries: the factor also packed and copied to host_dst panel by panel
+int fwd_streamed(smg_ctx* ctx, chol_fwd_args a, double* ws, int* started, double* packed, double* host_dst,
+                 int marker_base) {
+  if (!started || !packed || !host_dst || marker_base < 0) return SMG_ERR_ARG;
+  *started = 0;
+  if (ws && !a.Dinv) return SMG_ERR_ARG;
+  if (marker_base + smg_cholesky_stream_panels(a.n) > 64) return SMG_ERR_ARG;
+  if (!ctx || smg_zero_stream_begin(ctx) != SMG_OK) return SMG_ERR_HIP;
+  const chol_stream_sink sink{packed, host_dst, marker_base};
+  a.inv_ws = ws;
+  a.inv_started = started;
+  a.sink = &sink;
+  const int rc = chol_fwd(ctx, a);
+  // an error after some panel copies were queued: they still target host_dst,
+  // which the caller may free or regrow once this returns
+  if (rc != SMG_OK) {
+    hipStreamSynchronize(ctx->zero_stream);
+    if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
+  }
+  return rc;
+}
 
 }  // namespace
 
@@ -1673,54 +1728,44 @@ int smg_check_symmetric(smg_ctx* ctx, const double* A, int lda, int n) {
 
 int smg_cholesky_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                      double* Dinv) {
-  return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, false);
+  return chol_fwd(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, false, false));
 }
 
 int smg_cholesky_fwd_checked(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                              double* Dinv) {
-  return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true);
+  return chol_fwd(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, true, false));
 }
 
 int smg_cholesky_fwd_checked_mark(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                                   double* Dinv) {
-  return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true, true);
+  return chol_fwd(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, true, true));
 }
 
 int smg_cholesky_fwd_checked_mark_inv(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                                       double* Dinv, double* ws, int* started) {
-  if (!started) return SMG_ERR_ARG;
-  *started = 0;
-  if (ws && !Dinv) return SMG_ERR_ARG;
-  return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true, true, ws, started);
+  return fwd_with_inverse(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, true, true), ws, started, false);
 }
 
 int smg_cholesky_fwd_checked_mark_winv(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                                        double* Dinv, double* ws, int* started) {
-  if (!started) return SMG_ERR_ARG;
-  *started = 0;
-  if (!ws || !Dinv) return SMG_ERR_ARG;
-  return chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true, true, ws, started, nullptr, true);
+  return fwd_with_inverse(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, true, true), ws, started, true);
 }
 
 int smg_cholesky_fwd_gp_mark(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv) {
   if (!src) return SMG_ERR_ARG;
-  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, nullptr, nullptr, nullptr, false, src);
+  return chol_fwd(ctx, fwd_described(src, L, ldl, Dinv));
 }
 
 int smg_cholesky_fwd_gp_mark_inv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv, double* ws,
                                  int* started) {
-  if (!started || !src) return SMG_ERR_ARG;
-  *started = 0;
-  if (ws && !Dinv) return SMG_ERR_ARG;
-  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, nullptr, false, src);
+  if (!src) return SMG_ERR_ARG;  // (before *started is written, as a NULL started)
+  return fwd_with_inverse(ctx, fwd_described(src, L, ldl, Dinv), ws, started, false);
 }
 
 int smg_cholesky_fwd_gp_mark_winv(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv, double* ws,
                                   int* started) {
-  if (!started || !src) return SMG_ERR_ARG;
-  *started = 0;
-  if (!ws || !Dinv) return SMG_ERR_ARG;
-  return chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, nullptr, true, src);
+  if (!src) return SMG_ERR_ARG;
+  return fwd_with_inverse(ctx, fwd_described(src, L, ldl, Dinv), ws, started, true);
 }
 
 int smg_cholesky_inverse_wait(smg_ctx* ctx) {
@@ -1735,36 +1780,13 @@ int smg_cholesky_stream_panels(int n) { return n <= 0 ? 0 : smg_ceil_div(n, n > 
 int smg_cholesky_fwd_checked_mark_stream(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl,
                                          double* Dinv, double* ws, int* started, double* packed, double* host_dst,
                                          int marker_base) {
-  if (!started || !packed || !host_dst || marker_base < 0) return SMG_ERR_ARG;
-  *started = 0;
-  if (ws && !Dinv) return SMG_ERR_ARG;
-  if (marker_base + smg_cholesky_stream_panels(n) > 64) return SMG_ERR_ARG;
-  if (!ctx || smg_zero_stream_begin(ctx) != SMG_OK) return SMG_ERR_HIP;
-  const chol_stream_sink sink{packed, host_dst, marker_base};
-  const int rc = chol_fwd(ctx, A, lda, n, L, ldl, Dinv, true, true, ws, started, &sink);
-  // an error after some panel copies were queued: they still target host_dst,
-  // which the caller may free or regrow once this returns
-  if (rc != SMG_OK) {
-    hipStreamSynchronize(ctx->zero_stream);
-    if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
-  }
-  return rc;
+  return fwd_streamed(ctx, fwd_stored(A, lda, n, L, ldl, Dinv, true, true), ws, started, packed, host_dst, marker_base);
 }
 
 int smg_cholesky_fwd_gp_mark_stream(smg_ctx* ctx, const smg_gp_source* src, double* L, int ldl, double* Dinv,
                                     double* ws, int* started, double* packed, double* host_dst, int marker_base) {
-  if (!started || !packed || !host_dst || marker_base < 0 || !src) return SMG_ERR_ARG;
-  *started = 0;
-  if (ws && !Dinv) return SMG_ERR_ARG;
-  if (marker_base + smg_cholesky_stream_panels(src->n) > 64) return SMG_ERR_ARG;
-  if (!ctx || smg_zero_stream_begin(ctx) != SMG_OK) return SMG_ERR_HIP;
-  const chol_stream_sink sink{packed, host_dst, marker_base};
-  const int rc = chol_fwd(ctx, nullptr, 0, src->n, L, ldl, Dinv, true, true, ws, started, &sink, false, src);
-  if (rc != SMG_OK) {  // (as smg_cholesky_fwd_checked_mark_stream: queued copies still target host_dst)
-    hipStreamSynchronize(ctx->zero_stream);
-    if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
-  }
-  return rc;
+  if (!src) return SMG_ERR_ARG;
+  return fwd_streamed(ctx, fwd_described(src, L, ldl, Dinv), ws, started, packed, host_dst, marker_base);
 }
 
 int smg_cholesky_stream_panel_cols(int n, int p, int* j0, int* j1) {
@@ -1780,35 +1802,70 @@ int smg_cholesky_stream_panel_cols(int n, int p, int* j0, int* j1) {
 
 namespace {
 
-int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, double* Dinv,
-             bool check_sym, bool mark, double* inv_ws, int* inv_started, const chol_stream_sink* sink,
-             bool w_only, const smg_gp_source* src) {
-  // src: the input described (A unused): generated into L in place of the copy
-  if (src && (!ctx || !smg_gp_source_ok(src) || src->n != n || (n > 0 && (!L || ldl < n)))) return SMG_ERR_ARG;
-  if (!src && (!ctx || n < 0 || (n > 0 && (!A || !L || lda < n || ldl < n)))) return SMG_ERR_ARG;
+// launch geometry of k_chol_panel for the panel of columns [J, K) of n
+struct panel_geom {
+  int grid;      // workgroup 0 = diagonal chain, the inverter, the tiles' owners
+  int nha, nhb;  // column helpers A (panel tiles 3..), B (tiles 4..), launched behind `grid`
+  int paired;    // one owner per pair of 32-row tiles below the panel
+};
+panel_geom panel_geometry(int n, int J, int K) {
+  const int nb = smg_ceil_div(K - J, SMG_NB);
+  // workgroup 0 = diagonal chain; tiles 1 .. T-1 over the others
+  const int T = panel_tiles(n, J, nb);
+  // chain, inverter, owners of tiles 1..T-1; paired: owners of the panel
+  // tiles 1..nb-1 and one workgroup per pair of 32-row tiles below
+  const int npairs = (T - nb + 1) / 2;
+  panel_geom g;
+  g.paired = nb + 1 + npairs <= PANEL_MAX_GRID + 1 - (nb > 3 ? 2 * nb - 7 : 0) ? 1 : 0;
+  g.grid = g.paired ? nb + 1 + npairs : (T < PANEL_MAX_GRID ? T : PANEL_MAX_GRID) + 1;
+  // column helpers for panel tiles 3 .. nb-1
+  g.nha = nb > 3 ? nb - 3 : 0;
+  g.nhb = nb > 4 ? nb - 4 : 0;
+  if (g.grid + g.nha + g.nhb > PANEL_MAX_GRID + 1 || nb > T) g.nha = g.nhb = 0;
+  return g;
+}
+
+// the time, us, that the side stream has behind the trailing update (b) of
+// the panel [J, K) before the next one becomes ready: the next panel [K, K2)
+// (~22 us per 64-column step) and its look-ahead (a), at ~30 TF/s, minus (b)
+// itself at ~40 TF/s
+double prog_slack_us(int n, int J, int K, int K2) {
+  const double m2 = n - K2, kk = K - J;
+  return 22.0 * (K2 - K) / SMG_NB + 6.0 + (double)(n - K) * (K2 - K) * kk / 30e6 -
+         (K2 < n ? 6.0 + m2 * m2 * kk / 40e6 : 0.0);
+}
+
+int chol_fwd(smg_ctx* ctx, const chol_fwd_args& a) {
+  const double* const A = a.A;
+  double* const L = a.L;
+  double* const inv_ws = a.inv_ws;
+  const int lda = a.lda, n = a.n, ldl = a.ldl;
+  const bool w_only = a.w_only;
+  if (a.src && (!ctx || !smg_gp_source_ok(a.src) || a.src->n != n || (n > 0 && (!L || ldl < n)))) return SMG_ERR_ARG;
+  if (!a.src && (!ctx || n < 0 || (n > 0 && (!A || !L || lda < n || ldl < n)))) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
   smg_prof_scope prof(ctx, SMG_FAM_CHOL_FWD);
-  double* aux = Dinv;
+  double* aux = a.Dinv;
   if (!aux) {
     aux = smg_ws(ctx, SMG_WS_TMP2, (size_t)smg_cholesky_aux_doubles(n));
     if (!aux) return SMG_ERR_OOM;
   }
-  Dinv = aux;  // the SMG_NB level comes first
+  double* const Dinv = aux;  // the SMG_NB level comes first
   const int tb = smg_ceil_div(n, 64);
-  if (src) {
-    if (int e = smg_gp_chol_source_launch(ctx, src, L, ldl)) return e;
+  if (a.src) {
+    if (int e = smg_gp_chol_source_launch(ctx, a.src, L, ldl)) return e;
   } else if (A != L || lda != ldl) {
-    if (check_sym && n % 64 == 0 && lda % 2 == 0 && ldl % 2 == 0 &&
+    if (a.check_sym && n % 64 == 0 && lda % 2 == 0 && ldl % 2 == 0 &&
         ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(L)) & 15) == 0)
       hipLaunchKernelGGL(k_check_symmetric_copy2, dim3(tb * (tb + 1) / 2), dim3(256), 0,
                          ctx->stream, A, lda, n, ctx->status_d, L, ldl);
-    else if (check_sym)
+    else if (a.check_sym)
       hipLaunchKernelGGL(k_check_symmetric_copy, dim3(tb * (tb + 1) / 2), dim3(256), 0, ctx->stream, A,
                          lda, n, ctx->status_d, L, ldl);
     else
       hipLaunchKernelGGL(k_copy_lower, dim3(grid_for((long long)n * n)), dim3(256), 0, ctx->stream,
                          A, lda, n, L, ldl);
-  } else if (check_sym) {
+  } else if (a.check_sym) {
     hipLaunchKernelGGL(k_check_symmetric, dim3(tb * (tb + 1) / 2), dim3(256), 0, ctx->stream, A, lda,
                        n, ctx->status_d);
   }
@@ -1840,33 +1897,31 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
   // the last panel only that panel's own block row remains.  (On a stream of
   // their own the rows ran 2x slower overall: with GPU_MAX_HW_QUEUES = 4 a
   // fifth stream shares a hardware queue with another, here the panels'.)
-  const bool prog = inv_ws && look && NB2 == SMG_NBR && smg_inv_prog_ok(n) && smg_inv_events(ctx) == SMG_OK;
+  // The rows' latency-bound parts need the zeroing stream (below): without
+  // one the factorisation is not progressive, as for any other n.
+  const bool prog = inv_ws && look && NB2 == SMG_NBR && smg_inv_prog_ok(n) && smg_inv_events(ctx) == SMG_OK &&
+                    smg_zero_stream_begin(ctx) == SMG_OK;
+  int nev = 0;       // pooled events used
+  hipEvent_t init_ev = nullptr;  // side behind the work queued so far (the zeroing stream's parts follow it)
   if (prog) {  // side follows the work queued so far (earlier readers of ws)
     SMG_HIP_TRY(hipEventRecord(ctx->inv_ev_main, ctx->stream));
     SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->inv_ev_main, 0));
-    smg_on_side on(ctx);
-    if (int rc = smg_inv_prog_init(ctx, n, inv_ws)) return rc;
-  }
-  int nev = 0;       // pooled events used
-  hipEvent_t init_ev = nullptr;  // C's zeroing on side (the zeroing stream's parts follow it)
-  if (prog) {
     if (!(init_ev = smg_event(ctx, nev++))) return SMG_ERR_HIP;
     SMG_HIP_TRY(hipEventRecord(init_ev, ctx->side));
   }
   hipEvent_t F = nullptr;  // the pending (b) on the side stream
-  // the block rows' parts (smg_inv_prog_row) queued on `side` behind each
-  // trailing update (b)_p within the slack before (b)_{p+1} becomes ready
-  // (the next panel and its look-ahead (a), minus (b)_p itself): queued
-  // whole, the growing rows held back (b)_{p+1}, the next (a) waiting for it,
-  // and with it the next panel; what does not fit goes after the last panel
-  int q_k = 0, q_part = 0;  // the next part to queue (all parts on `side`)
+  // the block rows' K^{-1} shares (smg_inv_prog_row, part 2) queued on `side`
+  // behind each trailing update (b)_p within the slack before (b)_{p+1}
+  // becomes ready (the next panel and its look-ahead (a), minus (b)_p itself):
+  // queued whole, the growing rows held back (b)_{p+1}, the next (a) waiting
+  // for it, and with it the next panel; what does not fit goes after the last
+  // panel
   const int rows_prog = prog ? n / SMG_NBR : 0;
-  // With the zeroing stream (idle during the panels): a row's chain of
+  // On the zeroing stream (idle during the panels): a row's chain of
   // latency-bound parts -- its 256/512-level inverses (~8 small launches),
   // W_{k,0:k} and Y_{k+1} -- runs there as soon as its panel is done (pe_ev);
   // only the K^{-1} shares (part 2, the bulk) go on `side` within the slack,
   // each after its row's W (w_ev).  C's accumulation order stays the rows'.
-  const bool zero_parts = prog && smg_zero_stream_begin(ctx) == SMG_OK;
   std::vector<hipEvent_t> pe_ev(rows_prog, nullptr), w_ev(rows_prog, nullptr);
   int z_k = 0, s_k = 0;  // next row for the zeroing stream's parts / the next share
   auto queue_zero = [&](int kmax) -> int {
@@ -1874,14 +1929,12 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       if (!pe_ev[z_k] || !(w_ev[z_k] = smg_event(ctx, nev++))) return SMG_ERR_HIP;
       if (z_k == 0) SMG_HIP_TRY(hipStreamWaitEvent(ctx->zero_stream, init_ev, 0));
       SMG_HIP_TRY(hipStreamWaitEvent(ctx->zero_stream, pe_ev[z_k], 0));
-      hipStream_t keep = ctx->stream;
-      ctx->stream = ctx->zero_stream;
+      smg_on_stream on(ctx, ctx->zero_stream);
       int rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, z_k, 0, true);
       if (!rc) rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, z_k, 1, true);
       if (!rc && hipEventRecord(w_ev[z_k], ctx->zero_stream) != hipSuccess) rc = SMG_ERR_HIP;
       if (!rc) rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, z_k, 3, true);  // the next row's Y
       if (!rc) rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, z_k, 4, true);  // the later rows' Y
-      ctx->stream = keep;
       if (rc) return rc;
       ++z_k;
     }
@@ -1893,67 +1946,36 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
     // 80 374.5, 150 375.3 evals/s)
     constexpr double tol = 40.0;
     while (s_k < z_k) {
-      const double c = smg_inv_prog_cost(n, s_k, 2, true);
+      const double c = smg_inv_share_cost(s_k);
       if (budget_us >= 0 && c > budget_us + tol) break;
       budget_us -= c;
       SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, w_ev[s_k], 0));
-      smg_on_side on(ctx);
+      smg_on_stream on(ctx, ctx->side);
       if (int rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, s_k, 2, true)) return rc;
       ++s_k;
-    }
-    return SMG_OK;
-  };
-  auto queue_parts = [&](int kmax, double budget_us) -> int {  // budget < 0: all of rows <= kmax
-    if (zero_parts) {
-      if (int rc = queue_zero(kmax)) return rc;
-      return queue_shares(budget_us);
-    }
-    static const int order[5] = {0, 1, 3, 4, 2};  // W_k first, then its Y contributions, its share last
-    const int nparts = w_only ? 4 : 5;
-    while (q_k <= kmax && q_k < rows_prog - 1) {
-      const double c = smg_inv_prog_cost(n, q_k, order[q_part], true);
-      if (budget_us >= 0 && c > budget_us + 40.0) break;
-      budget_us -= c;
-      smg_on_side on(ctx);
-      if (int rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, q_k, order[q_part], true)) return rc;
-      if (++q_part == nparts) {
-        q_part = 0;
-        ++q_k;
-      }
     }
     return SMG_OK;
   };
   for (int J = 0; J < n; J += NB2) {
     const int K = min(J + NB2, n);
     {  // the whole panel in one persistent launch (k_chol_panel)
-      // workgroup 0 = diagonal chain; tiles 1 .. T-1 over the others
-      const int T = panel_tiles(n, J, smg_ceil_div(K - J, SMG_NB));
-      // chain, inverter, owners of tiles 1..T-1; paired: owners of the panel
-      // tiles 1..nb-1 and one workgroup per pair of 32-row tiles below
-      const int nbq = smg_ceil_div(K - J, SMG_NB);
-      const int npairs = (T - nbq + 1) / 2;
-      const int paired = nbq + 1 + npairs <= PANEL_MAX_GRID + 1 - (nbq > 3 ? 2 * nbq - 7 : 0) ? 1 : 0;
-      const int grid = paired ? nbq + 1 + npairs : (T < PANEL_MAX_GRID ? T : PANEL_MAX_GRID) + 1;
+      const panel_geom g = panel_geometry(n, J, K);
       const int epoch = ++ctx->flag_epoch;
       ctx->status_armed = 1;
-      // column helpers for panel tiles 3 .. nb-1
-      const int nbp = smg_ceil_div(K - J, SMG_NB);
-      int nha = nbp > 3 ? nbp - 3 : 0, nhb = nbp > 4 ? nbp - 4 : 0;  // helpers A (tiles 3..), B (tiles 4..)
-      if (grid + nha + nhb > PANEL_MAX_GRID + 1 || nbp > T) nha = nhb = 0;
       smg_prof_scope pprof(ctx, SMG_FAM_PANEL);  // (the launch alone: bench.py's dominant-kernel roofline)
       if (ctx->prof_on) {  // in-panel work: the diagonal block's factor + the rows below's solve
         const double m = n - J, b = K - J;
         ctx->prof_flops[SMG_FAM_PANEL] += m * b * b - 2.0 * b * b * b / 3.0;
       }
       panel_host_stamp(epoch);
-      hipLaunchKernelGGL(k_chol_panel, dim3(grid + nha + nhb), dim3(SMG_DIAG_THREADS), 0, ctx->stream, L, ldl,
-                         n, J, K, Dinv, n, ctx->flags_d, epoch, ctx->status_d, grid, nha, paired);
+      hipLaunchKernelGGL(k_chol_panel, dim3(g.grid + g.nha + g.nhb), dim3(SMG_DIAG_THREADS), 0, ctx->stream, L, ldl,
+                         n, J, K, Dinv, n, ctx->flags_d, epoch, ctx->status_d, g.grid, g.nha, g.paired);
     }
-    if (zero_parts && J / NB2 < rows_prog) {  // this panel is final: its block row's inverses may start
+    if (J / NB2 < rows_prog) {  // this panel is final: its block row's inverses may start
       if (!(pe_ev[J / NB2] = smg_event(ctx, nev++))) return SMG_ERR_HIP;
       SMG_HIP_TRY(hipEventRecord(pe_ev[J / NB2], ctx->stream));
     }
-    if (sink) {  // columns [J, K) are final: packed and copied to the host on the copy stream
+    if (const chol_stream_sink* sink = a.sink) {  // columns [J, K) are final: packed, copied to the host (copy stream)
       // (on the zeroing stream each copy held back the block-row chain queued behind it, the K^{-1}
       // shares waiting for that, and the trailing updates queued after those: in a gp_eigen trace the
       // eight panels spanned 4.8 ms with the copies at 28 GB/s, 3.3 ms at 55 GB/s on a stream of their own)
@@ -1967,11 +1989,10 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       if (int rc = smg_marker_event(ctx, sink->marker_base + J / NB2, &Me)) return rc;
       SMG_HIP_TRY(hipEventRecord(Pe, ctx->stream));
       SMG_HIP_TRY(hipStreamWaitEvent(cs, Pe, 0));
-      hipStream_t keep = ctx->stream;
-      ctx->stream = cs;
-      const int prc = smg_pack_tril_cols(ctx, n, L, ldl, J, K, sink->packed);
-      ctx->stream = keep;
-      if (prc) return prc;
+      {
+        smg_on_stream on(ctx, cs);
+        if (int rc = smg_pack_tril_cols(ctx, n, L, ldl, J, K, sink->packed)) return rc;
+      }
       const size_t o0 = (size_t)J * n - (size_t)J * (J - 1) / 2, o1 = (size_t)K * n - (size_t)K * (K - 1) / 2;
       if (int rc = smg_d2h_impl(ctx, cs, sink->host + o0, sink->packed + o0, (o1 - o0) * sizeof(double))) return rc;
       SMG_HIP_TRY(hipEventRecord(Me, cs));
@@ -2004,7 +2025,7 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       // 355-358 -> 358-360 evals/s in a same-box A/B)
       const int K3 = min(K2 + NB2, n);
       {
-        smg_on_side on(ctx);
+        smg_on_stream on(ctx, ctx->side);
         rc = smg_gemm_impl(ctx, 0, 1, 1, m2, K3 - K2, K - J, -1.0, P2, ldl, P2, ldl, 1.0,
                            L + K2 + (size_t)K2 * ldl, ldl);
       }
@@ -2015,7 +2036,7 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       if (K3 < n) {  // (b2)
         const int m3 = n - K3;
         const double* P3 = L + K3 + (size_t)J * ldl;
-        smg_on_side on(ctx);
+        smg_on_stream on(ctx, ctx->side);
         if ((rc = smg_gemm_impl(ctx, 0, 1, 1, m3, m3, K - J, -1.0, P3, ldl, P3, ldl, 1.0, L + K3 + (size_t)K3 * ldl,
                                 ldl)))
           return rc;
@@ -2024,34 +2045,32 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, E, 0));
     }
     if (prog) {  // (F is recorded before them: the next (a) does not wait for them)
-      // slack: the next panel (~22 us per 64-column step) and its (a), at
-      // ~30 TF/s, minus (b) at ~40 TF/s
-      const double m2 = n - K2, kk = K - J;
-      const double slack = 22.0 * (K2 - K) / SMG_NB + 6.0 + (double)(n - K) * (K2 - K) * kk / 30e6 -
-                           (K2 < n ? 6.0 + m2 * m2 * kk / 40e6 : 0.0);
-      // queued against HALF that estimate: since the K^{-1} / Y parts stopped clearing their outputs and
+      // queued against HALF the slack estimate: since the K^{-1} / Y parts stopped clearing their outputs and
       // the block-row inverses became one launch, the full estimate measures slower
       // (same-box A/Bs of the scale, r05y / r05z2 / r05z3: 0.5 380.5 and 379.9, 0.65 379.0, 1.0 374.8
       // and 376.0, 0.4 371, 0.25 373.6, 0 370.6 evals/s)
-      if ((rc = queue_parts(J / NB2, SMG_PROG_SLACK_SCALE * slack))) return rc;
+      if ((rc = queue_zero(J / NB2))) return rc;
+      if ((rc = queue_shares(SMG_PROG_SLACK_SCALE * prog_slack_us(n, J, K, K2)))) return rc;
     }
   }
   if (prog) {  // the rest of the rows but the last
-    if (int rc0 = queue_parts(rows_prog - 2, -1.0)) return rc0;
+    if (int rc0 = queue_zero(rows_prog - 2)) return rc0;
+    if (int rc0 = queue_shares(-1.0)) return rc0;
   }
   // every launch that can latch the status (the symmetric check, the panels'
   // not-PD and hand-off bits) is enqueued: the status mark goes here, so a
   // host waiting on it does not also wait for the block inverses below
-  if (mark) {
+  if (a.mark) {
     const int rc = smg_status_mark_impl(ctx);
     if (rc) return rc;
   }
   if (F) SMG_HIP_TRY(hipStreamWaitEvent(ctx->stream, F, 0));
   // the 128-, 256- and 512-block inverses (reverse pass, triangular solves);
-  // progressive: every block row's but the last were formed on `side`, the
-  // last one's here on the main stream (idle after the last panel), then the
-  // last block row of W and its K^{-1} update go to `side`, overlapping the
-  // MVN's forward solves and the host's work up to the reverse
+  // progressive: every block row's but the last were formed behind their
+  // panels, the last one's here on the main stream (idle after the last
+  // panel), then the last block row of W goes to the zeroing stream and its
+  // K^{-1} update to `side`, overlapping the MVN's forward solves and the
+  // host's work up to the reverse
   int rc;
   if (prog) {
     const int r0 = n - SMG_NBR;
@@ -2062,32 +2081,23 @@ int chol_fwd(smg_ctx* ctx, const double* A, int lda, int n, double* L, int ldl, 
       return rc;
     SMG_HIP_TRY(hipEventRecord(ctx->inv_ev_main, ctx->stream));
     const int klast = n / SMG_NBR - 1;
-    if (zero_parts) {  // W_last on the zeroing stream behind the last Y, its share on side
-      SMG_HIP_TRY(hipStreamWaitEvent(ctx->zero_stream, ctx->inv_ev_main, 0));
-      hipStream_t keep = ctx->stream;
-      ctx->stream = ctx->zero_stream;
+    // W_last on the zeroing stream behind the last Y, its share on side (it adds to no later row's Y)
+    SMG_HIP_TRY(hipStreamWaitEvent(ctx->zero_stream, ctx->inv_ev_main, 0));
+    {
+      smg_on_stream on(ctx, ctx->zero_stream);
       rc = wkk ? SMG_OK : smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, klast, 0, false);
       if (!rc) rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, klast, 1, false);
-      ctx->stream = keep;
-      if (rc) return rc;
-      if ((rc = record_w_ready(ctx, ctx->zero_stream))) return rc;
-      SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->inv_ev_w, 0));
-      smg_on_side on(ctx);
-      if (!w_only && (rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, klast, 2, false))) return rc;
-    } else {
-      SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->inv_ev_main, 0));
-      smg_on_side on(ctx);
-      for (int part = 0; part < (w_only ? 2 : 3); ++part) {  // (the last row adds to no later row's Y)
-        if (part == 0 && wkk) continue;
-        if ((rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, klast, part, false))) return rc;
-        if (part == 1 && (rc = record_w_ready(ctx, ctx->side))) return rc;
-      }
     }
+    if (rc) return rc;
+    if ((rc = record_w_ready(ctx, ctx->zero_stream))) return rc;
+    SMG_HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->inv_ev_w, 0));
+    smg_on_stream on(ctx, ctx->side);
+    if (!w_only && (rc = smg_inv_prog_row(ctx, L, ldl, aux, n, inv_ws, klast, 2, false))) return rc;
     // its writes to ws are joined before anything on the main stream may
     // touch ws (smg_cholesky_mvn_rev_v / smg_join_async)
     SMG_HIP_TRY(hipEventRecord(ctx->inv_ev, ctx->side));
     ctx->inv_pending = 1;
-    *inv_started = w_only ? 3 : 2;
+    *a.inv_started = w_only ? 3 : 2;
   } else if ((rc = chol_block_inverses(ctx, L, ldl, aux, n, 0, -1, nullptr, true))) {
     return rc;
   }

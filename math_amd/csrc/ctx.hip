@@ -134,9 +134,9 @@ static void prof_drain(smg_ctx* ctx) {
 double* smg_ws(smg_ctx* ctx, int id, size_t doubles) {
   if (doubles > ctx->ws_doubles[id]) {
     if (ctx->ws[id]) {
-      hipStreamSynchronize(ctx->stream);
+      hipStreamSynchronize(ctx->stream);  // (the current target: a workspace grown under a redirection)
       if (ctx->side) hipStreamSynchronize(ctx->side);
-      if (ctx->main_stream) hipStreamSynchronize(ctx->main_stream);
+      hipStreamSynchronize(ctx->main_stream);
       hipFree(ctx->ws[id]);
     }
     size_t n = doubles < (1u << 18) ? (1u << 18) : doubles + doubles / 4;
@@ -235,7 +235,6 @@ int smg_ctx_create(int device, size_t initial, smg_ctx** out) {
   ctx->inv_pending = 0;
   ctx->inv_w_recorded = 0;
   ctx->side = nullptr;
-  ctx->main_stream = nullptr;
   for (int i = 0; i < SMG_FAM_COUNT; ++i) {
     ctx->prof_ms[i] = 0;
     ctx->prof_count[i] = 0;
@@ -251,6 +250,7 @@ int smg_ctx_create(int device, size_t initial, smg_ctx** out) {
     delete ctx;
     return SMG_ERR_HIP;
   }
+  ctx->main_stream = ctx->stream;  // (never written again: `stream` alone moves, under smg_on_stream)
   if (initial < (size_t)(64u << 20)) initial = (size_t)(64u << 20);
   char* base = nullptr;
   if (hipMalloc(&base, initial) != hipSuccess) {
@@ -334,7 +334,7 @@ int smg_ctx_destroy(smg_ctx* ctx) {
 }
 
 int smg_ctx_device(const smg_ctx* ctx) { return ctx ? ctx->device : -1; }
-void* smg_ctx_stream(smg_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+void* smg_ctx_stream(smg_ctx* ctx) { return ctx ? (void*)ctx->main_stream : nullptr; }
 
 void* smg_arena_alloc(smg_ctx* ctx, size_t bytes) {
   if (!ctx) return nullptr;
@@ -408,8 +408,7 @@ size_t smg_arena_reserved(const smg_ctx* ctx) {
 // every stream that may still have a copy into / out of pinned host memory
 // in flight (the streamed factor's panel copies run on the zeroing stream)
 static void sync_all_streams(smg_ctx* ctx) {
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->main_stream && ctx->main_stream != ctx->stream) hipStreamSynchronize(ctx->main_stream);
+  hipStreamSynchronize(ctx->main_stream);
   if (ctx->side) hipStreamSynchronize(ctx->side);
   if (ctx->zero_stream) hipStreamSynchronize(ctx->zero_stream);
   if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
@@ -637,8 +636,7 @@ int smg_zero_flush(smg_ctx* ctx) {
   if (ctx->zero_queue.empty()) return SMG_OK;
   // after everything already enqueued on the main stream (the memory may have
   // belonged to a recovered tape whose kernels are still queued there)
-  hipStream_t main = (ctx->side && ctx->stream == ctx->side) ? ctx->main_stream : ctx->stream;
-  SMG_HIP_TRY(hipEventRecord(ctx->zero_ev_main, main));
+  SMG_HIP_TRY(hipEventRecord(ctx->zero_ev_main, ctx->main_stream));
   SMG_HIP_TRY(hipStreamWaitEvent(ctx->zero_stream, ctx->zero_ev_main, 0));
   // at most 128 workgroups: these zeroings (the N^2 adjoints of a GP's K, K + dI
   // and L: 400 MB at N = 4096) run beside the first panel, and at full width

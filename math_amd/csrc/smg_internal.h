@@ -34,11 +34,13 @@ constexpr size_t SMG_STATUS_BYTES = 256 + 4096 * sizeof(int) + SMG_INV_CTRS * si
 
 struct smg_ctx {
   int device;
-  hipStream_t stream;       // the tape's stream: every entry point's work is ordered on it
+  // the stream the next launch goes to: main_stream, or another of the
+  // context's streams while an smg_on_stream redirects to it
+  hipStream_t stream;
   // look-ahead side stream of the blocked factorizations (created lazily);
   // work issued there is joined back into `stream` before the entry returns
   hipStream_t side;
-  hipStream_t main_stream;  // saved while `stream` temporarily points at `side`
+  hipStream_t main_stream;  // the tape's stream: every entry point's work is ordered on it (fixed at creation)
   std::vector<hipEvent_t> ev_pool;
   std::vector<hipEvent_t> ev_fork;  // smg_fork_event
   std::vector<hipEvent_t> marker_ev;  // smg_marker_record / smg_marker_wait (host pipelining)
@@ -174,27 +176,26 @@ hipEvent_t smg_event(smg_ctx* ctx, int i); // i-th pooled event (grown on demand
 // run two independent launches on the main and side streams at once (their
 // indices never meet chol_fwd's, which grow with the panel count)
 hipEvent_t smg_fork_event(smg_ctx* ctx, int i);
-// RAII: issue the enclosed launches on the side stream
-struct smg_on_side {
+// RAII: issue the enclosed launches on stream s (the previous target is kept
+// in the guard, so guards nest)
+struct smg_on_stream {
   smg_ctx* ctx;
-  explicit smg_on_side(smg_ctx* c) : ctx(c) {
-    ctx->main_stream = ctx->stream;
-    ctx->stream = ctx->side;
-  }
-  ~smg_on_side() { ctx->stream = ctx->main_stream; }
+  hipStream_t prev;
+  smg_on_stream(smg_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { ctx->stream = s; }
+  ~smg_on_stream() { ctx->stream = prev; }
 };
 
 // chol_mvn.hip: K^{-1} for the closed-form reverse formed progressively
 // during the factorisation, block row k of W = L^{-1} once panel k is final
 // (queued by chol_fwd on `side`); ws: smg_cholesky_mvn_rev_ws_doubles(n)
 bool smg_inv_prog_ok(int n);
-int smg_inv_prog_init(smg_ctx* ctx, int n, double* ws);
 // part 0..3 of block row k (W_kk, W_{k,0:k}, the K^{-1} share, Y_{k+1});
 // inverses_here: part 0 forms the block row's 128/256/512 inverses first,
-// then records inv_ev_aux.  smg_inv_prog_cost: its device time estimate, us.
+// then records inv_ev_aux.  smg_inv_share_cost: the device time estimate of
+// row k's K^{-1} share (part 2), us.
 int smg_inv_prog_row(smg_ctx* ctx, const double* L, int ldl, double* aux, int n, double* ws, int k, int part,
                      bool inverses_here);
-double smg_inv_prog_cost(int n, int k, int part, bool inverses_here);
+double smg_inv_share_cost(int k);
 // block inverses of the rows [row0, row0 + nrows) (multiples of 512), T: a
 // workspace (NULL: SMG_WS_TMP); Wout (ld n, may be NULL): the 512-level
 // block also written there when one launch forms it (*wrote)
