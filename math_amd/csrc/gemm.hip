@@ -24,7 +24,10 @@
 // triangular operands (tri, which also sets the tile order) and offset
 // triangles in the last rows of op(A) / columns of op(B) (cut_a / cut_b, which
 // leave the order alone and only spread the shortened tiles over the XCDs).
+// Which workgroup computes which tile over which K range, and the grid that
+// launches them, are host-and-device functions in gemm_tiles.h.
 #include "smg_internal.h"
+#include "gemm_tiles.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -68,6 +71,7 @@
 #endif
 
 namespace {
+using namespace gemm_tiles;
 
 // LDS images of the operand tiles, unpadded and XOR-swizzled so that both
 // the staging stores (32 consecutive elements along the contiguous dim per
@@ -190,40 +194,6 @@ __device__ __forceinline__ void store_tile(double* lds, const double (&r)[BM * B
   }
 }
 
-__device__ __forceinline__ void tri_decode(int t, int& bi, int& bj) {
-  // t -> (bi, bj) with bj <= bi, row-major over the lower triangle of tiles
-  int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while ((r + 1) * (r + 2) / 2 <= t) ++r;
-  while (r * (r + 1) / 2 > t) --r;
-  bi = r;
-  bj = t - r * (r + 1) / 2;
-}
-
-// t -> (bi, bj) over the lower triangle of T x T tiles in groups of 8 block
-// rows, each group column by column (its rows i >= j within a column): the
-// tiles in flight at once share a few A row panels and B column panels, where
-// the row-major order swept every B panel of a row before the next row
-__device__ __forceinline__ void tri_decode_grouped(int t, int T, int& bi, int& bj) {
-  constexpr int G = 8;
-  int r, c;
-  tri_decode(t, r, c);
-  const int r0 = r / G * G, r1 = min(r0 + G, T), h = r1 - r0;
-  int q = t - r0 * (r0 + 1) / 2;
-  if (q < r0 * h) {
-    bi = r0 + q % h;
-    bj = q / h;
-    return;
-  }
-  q -= r0 * h;
-  int j = r0;
-  while (q >= r1 - j) {
-    q -= r1 - j;
-    ++j;
-  }
-  bi = j + q;
-  bj = j;
-}
-
 // MODE: 0 = full C, 1 = lower / 2 = upper triangle of C only (BM == BN, m == n),
 //   3 = the lower triangle computed and stored mirrored too (a symmetric C
 //       from its lower half: no separate sym_from_lower pass),
@@ -240,6 +210,14 @@ __device__ __forceinline__ void tri_decode_grouped(int t, int T, int& bi, int& b
 // NB LDS buffers (64 x 64 tile only).  That path has no bounds handling: the
 // host takes it only for whole tiles, K ranges in whole stages and 16-byte
 // aligned operand pairs (dma_eligible).
+// The parameters stay scalars, and the pointers __restrict__ parameters.  As
+// one by-value struct the kernel took the same registers but loaded its fields
+// one by one where it first used them, a wait each time, and the short NN
+// products on 32 x 32 tiles ran 1.2 to 1.5 % longer ((1024,512,512) 19.15 ->
+// 19.44 us, 512^3 10.73 -> 10.85 us; profiles/gemm_args_ab.txt); and
+// __restrict__ has no effect on a struct's member: without it the in-place
+// forms' TN kernels took 222 VGPRs for 166.  The tile map's view of them, a
+// gemm_grid (gemm_tiles.h), is put together from the scalars below.
 template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1, int NB = 0>
 __global__ __launch_bounds__(256 * KS) void k_gemm(
     int m, int n, int k, double alpha, const double* __restrict__ A, int lda,
@@ -247,9 +225,9 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
     int ldc, int tiles_m, int ntiles, int kchunk, double* __restrict__ slab, long long sA,
     long long sB, long long sC, int px, int ntp, int tri, double* __restrict__ C2, int ldc2, int bz, int cut_a,
     int cut_b, int cut_spread) {
+  const gemm_grid g = {m, n, k, tri, cut_a, cut_b, cut_spread, tiles_m, 0, ntiles, px, ntp, 0, kchunk};  // (tn, splits: the host's)
   constexpr bool LOWT = MODE == 1 || MODE == 3;  // lower-triangle tiles
   constexpr bool UPT = MODE == 2;
-  constexpr bool TRIC = LOWT || UPT;
   // strided batch over blockIdx.y (sA = sB = sC = 0 for a single product)
   A += blockIdx.y * sA;
   B += blockIdx.y * sB;
@@ -271,133 +249,12 @@ __global__ __launch_bounds__(256 * KS) void k_gemm(
   constexpr int POOL = (OPS > (BM + 1) * ECH) ? OPS : (BM + 1) * ECH;
   __shared__ double pool[POOL];
 
-  int bi, bj, tile, split;
-  // A triangular operand gives every tile a K range set by its row (op(A))
-  // or column (op(B)) block.  The workgroups a CU holds at once are assigned
-  // by index, so an order in which that block index varied fastest gave each
-  // CU tiles of ONE block: the CUs of the long-K blocks carried ~2x the mean
-  // work (N^3 products with a triangular op(A) took 0.88x the full product's
-  // time instead of 0.5x).  Such grids run in the linear order (the launch
-  // sets px = 0) with that block index varying slowest, longest K first
-  // (N = 4096, op(A) upper: 2120 -> 1143 us; op(B) upper 1136 us).
-  const bool tri_a_only = !TRIC && (tri & 3) && !(tri & 12);
-  const bool tri_b_only = !TRIC && (tri & 12) && !(tri & 3);
-  if (px > 0) {
-    // XCD-aware placement (full / trapezoidal grids): workgroups b and b + 8
-    // share an XCD (round-robin dispatch), so XCD slot x = b % 8 takes one
-    // rectangle of a px x (8 / px) partition of the tile grid, column-major
-    // inside it; each XCD's L2 then holds 1/px of A's rows and px/8 of B's
-    // columns instead of all of both.  Grid: ntp = 8 x the largest rectangle
-    // per split; surplus workgroups exit.
-    split = blockIdx.x / ntp;
-    const int tb = blockIdx.x - split * ntp;
-    const int x = tb & 7, l = tb >> 3, py = 8 / px;
-    const int tiles_n = ntiles / tiles_m;
-    const int rx = x % px, ry = x / px;
-    const int r0 = rx * tiles_m / px, r1 = (rx + 1) * tiles_m / px;
-    const int c0 = ry * tiles_n / py, c1 = (ry + 1) * tiles_n / py;
-    const int rm = r1 - r0;
-    // cut_b: the tile columns from the cut on run ever shorter K ranges, and
-    // they are the last ones: in contiguous column ranges the XCDs of the
-    // last range(s) idle while the others set the kernel's time.  The columns
-    // are dealt round-robin instead (XCD column slot ry takes ry, ry + py,
-    // ...): as many column panels of B per XCD as before, the short ones last.
-    const bool deal = cut_spread && cut_b >= 0;
-    const int nc = deal ? (tiles_n - ry + py - 1) / py : c1 - c0;
-    if (rm <= 0 || l >= rm * nc) return;
-    tile = (r0 + l % rm) + (deal ? ry + py * (l / rm) : c0 + l / rm) * tiles_m;
-  } else {
-    tile = blockIdx.x % ntiles;
-    split = blockIdx.x / ntiles;
-  }
-  // triangle modes: square C -> only the tiles of the triangle are launched
-  // (tri_decode); trapezoidal C (m != n, the panel updates of the two-level
-  // Cholesky) -> the full grid, tiles wholly outside the triangle exit
-  const bool tri_sq = TRIC && m == n && BM == BN;
-  if (LOWT && tri_sq) {
-    // lower-triangle grids in the order of decreasing K range under the
-    // triangular operands (see tri_a_only below): by column (op(B) lower:
-    // K in [j0, k)), by column from the right (op(B) upper: K below j0 + BN),
-    // by diagonal from the corner (both lower: K in [j0, i0 + BM)), by row
-    // from the bottom (op(A) lower alone), else by row from the top
-    const int T = tiles_m;
-    int r, q;
-    if (tri == SMG_TRI_B_LOWER) {
-      tri_decode(ntiles - 1 - tile, r, q);
-      bj = T - 1 - r;
-      bi = bj + q;
-    } else if (tri == SMG_TRI_B_UPPER || tri == (SMG_TRI_A_LOWER | SMG_TRI_B_UPPER)) {
-      tri_decode(tile, r, q);
-      bj = T - 1 - r;
-      bi = bj + q;
-    } else if (tri == (SMG_TRI_A_LOWER | SMG_TRI_B_LOWER)) {
-      tri_decode(tile, r, q);
-      bj = q;
-      bi = q + (T - 1 - r);
-    } else if (tri == SMG_TRI_A_LOWER) {
-      tri_decode(ntiles - 1 - tile, bi, bj);
-    } else if (tri == 0 && ntiles >= 64) {
-      // equal-work tiles (no K cut): XCD x (workgroups b = x mod 8, dispatched
-      // round-robin) takes one contiguous run of the grouped tile order, so
-      // its L2 holds a few row panels of A and column panels of B at a time
-      // (row-major over all XCDs, the last K^{-1} share fetched 530 MB
-      // against 151 MB algorithmic, r06 PMC)
-      // (cut_a: the tile rows from the cut on run ever shorter K ranges and
-      // come last in that order, all in the last XCDs' runs, which then idle
-      // while the others set the kernel's time.  The order is split at the
-      // first row group that reaches the cut -- nu tiles before it, a multiple
-      // of 8 -- and every XCD takes a run of each part, the short tiles last.)
-      const int b = tile, x = b & 7, l = b >> 3;
-      int nu = 0;
-      if (cut_spread && cut_a >= 0) {
-        const int g0 = min((cut_a + BM - 1) / BM, T) / 8 * 8;
-        nu = (g0 * (g0 + 1) / 2) & ~7;
-      }
-      const int rest = ntiles - nu, per = rest >> 3, extra = rest & 7;
-      const int t = l < (nu >> 3) ? x * (nu >> 3) + l : nu + x * per + (x < extra ? x : extra) + l - (nu >> 3);
-      tri_decode_grouped(t, tiles_m, bi, bj);
-    } else {
-      tri_decode(tile, bi, bj);
-    }
-  } else if (UPT && tri_sq) {
-    tri_decode(tile, bj, bi);
-  } else if (tri_a_only) {  // rows slowest, longest K first
-    const int r = tile / (ntiles / tiles_m);
-    bi = (tri & 1) ? tiles_m - 1 - r : r;
-    bj = tile % (ntiles / tiles_m);
-  } else if (tri_b_only) {  // columns slowest, longest K first
-    const int tn = ntiles / tiles_m, c = tile / tiles_m;
-    bi = tile % tiles_m;
-    bj = (tri & 8) ? tn - 1 - c : c;
-  } else {
-    bi = tile % tiles_m;
-    bj = tile / tiles_m;
-  }
-  if (LOWT && !tri_sq && bj * BN > bi * BM + BM - 1) return;
-  if (UPT && !tri_sq && bi * BM > bj * BN + BN - 1) return;
-  const int i0 = bi * BM, j0 = bj * BN;
-  int kbeg = split * kchunk;
-  int kend = min(k, kbeg + kchunk);
-  if (tri || cut_a >= 0 || cut_b >= 0) {
-    // triangular operands: only k where both op(A)(i, k) and op(B)(k, j) can
-    // be nonzero for some (i, j) of this tile (BK-aligned: the extra
-    // elements are stored zeros)
-    int lo = 0, hi = k;
-    if (tri & 1) hi = min(hi, i0 + BM);  // op(A) lower: zero for k > i
-    if (tri & 2) lo = max(lo, i0);       // op(A) upper: zero for k < i
-    if (tri & 4) lo = max(lo, j0);       // op(B) lower: zero for k < j
-    if (tri & 8) hi = min(hi, j0 + BN);  // op(B) upper: zero for k > j
-    // offset triangles (no say in the tile order, unlike tri): op(A)(i, k) = 0
-    // for k < i - cut_a in the rows i >= cut_a, op(B)(k, j) = 0 for
-    // k < j - cut_b in the columns j >= cut_b (a block row [X | T] of a lower
-    // triangular matrix, T its diagonal block: T's tile band starts at the cut)
-    if (cut_a >= 0 && i0 >= cut_a) lo = max(lo, i0 - cut_a);
-    if (cut_b >= 0 && j0 >= cut_b) lo = max(lo, j0 - cut_b);
-    lo = lo / BK * BK;
-    kbeg = max(kbeg, lo);
-    kend = min(kend, hi);
-    if (kend < kbeg) kend = kbeg;
-  }
+  // which tile of C this workgroup computes, over which K range (gemm_tiles.h)
+  const gemm_tile t = gemm_tile_of<BM, BN, MODE>(g, blockIdx.x);
+  if (!t.live) return;
+  const int split = t.split, i0 = t.bi * BM, j0 = t.bj * BN;
+  const gemm_krange kr = gemm_k_range<BM, BN, BK>(g, i0, j0, split);
+  const int kbeg = kr.kbeg, kend = kr.kend;
 
   constexpr int TM = BM / 32, TN = BN / 32;
   constexpr int NT = 256 * KS;
@@ -677,29 +534,40 @@ __global__ __launch_bounds__(256) void k_splitk_reduce2(int m, int n, int splits
   }
 }
 
-// the second output of MODE 4 (launch reads it from here: one product at a
-// time per host thread issues a MODE-4 GEMM)
-thread_local double* t_c2 = nullptr;
-thread_local int t_ldc2 = 0;
-// the beta-zero boundary of the next product (k_gemm's bz; smg_gemm_bz_impl)
-thread_local int t_bz = 0;
-// the offset triangular K cuts of the next product (k_gemm's cut_a / cut_b,
-// -1: none; smg_gemm_cut_impl)
-thread_local int t_cut_a = -1, t_cut_b = -1;
+// One product as it travels from an entry to launch:
+// C = alpha op(A) op(B) + beta C, `batch` of them at strides sA / sB / sC.
+struct gemm_args {
+  int m, n, k;
+  double alpha;
+  const double* A;
+  int lda;
+  const double* B;
+  int ldb;
+  double beta;
+  double* C;
+  int ldc, tri = 0;  // (tri: SMG_TRI_* bits)
+  int batch = 1;
+  long long sA = 0, sB = 0, sC = 0;
+  double* C2 = nullptr;  // the second output of MODE 4 and (optional: Phi) of MODE 3; null in every other mode
+  int ldc2 = 0;
+  int bz = 0;                 // the beta-zero boundary (k_gemm's bz; smg_gemm_bz_impl)
+  int cut_a = -1, cut_b = -1;  // the offset triangular K cuts (-1: none; smg_gemm_cut_impl)
+};
 
 // Multiply-adds x 2 that the offset cuts take off a product without triangular
-// operands, tile by tile as k_gemm skips them; a triangle of C counted by its
-// elements, as smg_gemm_impl counts the uncut product.
+// operands, tile by tile as k_gemm skips them (gemm_k_range); a triangle of C
+// counted by its elements, as smg_gemm_impl counts the uncut product.
 template <int BM, int BN, int BK>
-double cut_flops(int mode, int m, int n, int k, int cut_a, int cut_b) {
+double cut_flops(int mode, const gemm_grid& g) {
+  const int m = g.m, n = g.n;
   double f = 0.0;
   for (int j0 = 0; j0 < n; j0 += BN)
     for (int i0 = 0; i0 < m; i0 += BM) {
-      int lo = 0;
-      if (cut_a >= 0 && i0 >= cut_a) lo = i0 - cut_a;
-      if (cut_b >= 0 && j0 >= cut_b && j0 - cut_b > lo) lo = j0 - cut_b;
-      lo = lo / BK * BK;
-      if (lo > k) lo = k;
+      int lo = g.k;  // the K this tile skips: what its splits' ranges leave out
+      for (int s = 0; s < g.splits; ++s) {
+        const gemm_krange kr = gemm_k_range<BM, BN, BK>(g, i0, j0, s);
+        lo -= kr.kend - kr.kbeg;
+      }
       if (lo == 0) continue;
       const int i1 = i0 + BM < m ? i0 + BM : m, j1 = j0 + BN < n ? j0 + BN : n;
       double el = 0.0;
@@ -714,40 +582,14 @@ double cut_flops(int mode, int m, int n, int k, int cut_a, int cut_b) {
 }
 
 template <int BM, int BN, int BK, bool TA, bool TB, int MODE, int KS = 1, int NB = 0>
-int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
-           int lda, const double* B, int ldb, double beta, double* C, int ldc, int batch = 1,
-           long long sA = 0, long long sB = 0, long long sC = 0, int tri = 0) {
-  constexpr bool TRIC = MODE == 1 || MODE == 2 || MODE == 3;
-  const int tm = smg_ceil_div(m, BM), tn = smg_ceil_div(n, BN);
-  const int ntiles = (TRIC && m == n && BM == BN) ? tm * (tm + 1) / 2 : tm * tn;
+int launch(smg_ctx* ctx, const gemm_args& a) {
+  const int m = a.m, n = a.n;
   // (ctx->gemm_cut 0: every product ignores its offset cuts; 2: it takes them
   // in the uncut product's tile placement, smg_set_gemm_cut_mode)
-  const int cut_a = ctx->gemm_cut ? t_cut_a : -1, cut_b = ctx->gemm_cut ? t_cut_b : -1;
-  const int cut_spread = ctx->gemm_cut == 1;
-  if (ctx->prof_on && !tri && (cut_a >= 0 || cut_b >= 0))
-    ctx->prof_flops[SMG_FAM_GEMM] -= batch * cut_flops<BM, BN, BK>(MODE, m, n, k, cut_a, cut_b);
-  // split K when the tile grid cannot fill the 256 CUs and K is long
-  int splits = 1;
-  const int target = 512;
-  constexpr int KMIN = 64;  // shortest K chunk of a split
-  // (a grid that already covers every CU once keeps K whole while K is short:
-  // 512^3 with 32 x 32 tiles, 256 tiles: 12.3 us unsplit vs 15.9 us split
-  // in two plus the reduction)
-  const bool covers = ntiles >= 256 && k <= 1024;
-  // (triangular operands: every tile has its own K range, no split)
-  // (MODE 3 / 4 products -- the symbolic step's, with triangular operands --
-  // never split)
-  // (the DMA-staged kernel never splits: its K ranges are whole stages)
-  if (NB == 0 && !tri && MODE != 3 && MODE != 4 && batch == 1 && ntiles < target && !covers &&
-      k >= 2 * KMIN) {
-    splits = smg_ceil_div(target, ntiles);
-    const int maxs = k / KMIN;
-    if (splits > maxs) splits = maxs;
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-  }
-  int kchunk = smg_ceil_div(smg_ceil_div(k, splits), BK) * BK;
-  splits = smg_ceil_div(k, kchunk);
+  const gemm_grid g = gemm_plan<BM, BN, BK, MODE, NB>(m, n, a.k, a.tri, a.batch, ctx->gemm_cut, a.cut_a, a.cut_b);
+  if (ctx->prof_on && !a.tri && (g.cut_a >= 0 || g.cut_b >= 0))
+    ctx->prof_flops[SMG_FAM_GEMM] -= a.batch * cut_flops<BM, BN, BK>(MODE, g);
+  const int splits = g.splits;
   double* slab = nullptr;
   if (splits > 1) {
     // the side and zeroing streams have their own slabs so concurrent split-K
@@ -758,41 +600,19 @@ int launch(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
     slab = smg_ws(ctx, slot, (size_t)splits * m * n);
     if (!slab) return SMG_ERR_OOM;
   }
-  // XCD partition px x (8 / px) of a full tile grid minimising the per-XCD
-  // operand footprint (rows of A + columns of B, in tiles); triangle grids
-  // (tri_decode order) and grids too small to split keep the linear order
-  // (a triangular operand alone: the linear, longest-K-first order of the
-  // kernel's tile decode instead)
-  const bool tri_one = !TRIC && tri && (!(tri & 3) || !(tri & 12));
-  int px = 0, ntp = ntiles;
-  if (!(TRIC && m == n && BM == BN) && ntiles >= 64 && !tri_one) {
-    long long best = -1;
-    for (int p = 1; p <= 8; p *= 2) {
-      const int q = 8 / p;
-      if (p > tm || q > tn) continue;
-      const long long rr = smg_ceil_div(tm, p), cc = smg_ceil_div(tn, q);
-      const long long foot = rr * BM + cc * BN;
-      if (best < 0 || foot < best) {
-        best = foot;
-        px = p;
-        ntp = 8 * (int)(rr * cc);
-      }
-    }
-  }
-  hipLaunchKernelGGL((k_gemm<BM, BN, BK, TA, TB, MODE, KS, NB>), dim3(ntp * splits, batch), dim3(256 * KS), 0,
-                     ctx->stream, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tm,
-                     ntiles, kchunk, slab, sA, sB, sC, px, ntp, tri, MODE >= 3 ? t_c2 : nullptr,
-                     MODE >= 3 ? t_ldc2 : 0, t_bz, cut_a, cut_b, cut_spread);
+  hipLaunchKernelGGL((k_gemm<BM, BN, BK, TA, TB, MODE, KS, NB>), dim3(g.ntp * splits, a.batch), dim3(256 * KS), 0,
+                     ctx->stream, m, n, a.k, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, g.tm, g.ntiles, g.kchunk,
+                     slab, a.sA, a.sB, a.sC, g.px, g.ntp, a.tri, a.C2, a.ldc2, a.bz, g.cut_a, g.cut_b, g.cut_spread);
   if (splits > 1) {
     const long long tot = (long long)m * n;
     if ((m & 1) == 0) {
       const long long pairs = tot / 2;
       const int nb = (int)(pairs / 256 < 2048 ? (pairs + 255) / 256 : 2048);
-      hipLaunchKernelGGL(k_splitk_reduce2, dim3(nb), dim3(256), 0, ctx->stream, m, n, splits, slab, alpha, beta,
-                         C, ldc, MODE, t_bz);
+      hipLaunchKernelGGL(k_splitk_reduce2, dim3(nb), dim3(256), 0, ctx->stream, m, n, splits, slab, a.alpha, a.beta,
+                         a.C, a.ldc, MODE, a.bz);
     } else {
       hipLaunchKernelGGL(k_splitk_reduce, dim3(smg_ceil_div(tot, 256)), dim3(256), 0,
-                         ctx->stream, m, n, splits, slab, alpha, beta, C, ldc, MODE, t_bz);
+                         ctx->stream, m, n, splits, slab, a.alpha, a.beta, a.C, a.ldc, MODE, a.bz);
     }
   }
   SMG_LAUNCH_CHECK();
@@ -831,32 +651,35 @@ inline bool dma_eligible(int m, int n, int k, const double* A, int lda, const do
 }
 
 template <bool TA, bool TB, int MODE>
-int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double* A,
-                  int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri,
-                  bool aliased = false) {
+int dispatch_tile(smg_ctx* ctx, const gemm_args& a, bool aliased = false) {
   constexpr bool FULLC = MODE == 0 || MODE == 4;  // every tile of C computed
+  const int m = a.m, n = a.n, k = a.k, tri = a.tri;
   // In-place products (C aliases an operand: the blocked TRSMs C = C Dinv,
   // L21 = A21 Dinv^T, X_p = W_p B_p) are race-free only when every workgroup
   // owns whole rows (C aliases A) or whole columns (C aliases B) of C.
-  const bool alias_a = overlaps(A, lda, TA ? k : m, TA ? m : k, C, ldc, m, n);
-  const bool alias_b = overlaps(B, ldb, TB ? n : k, TB ? k : n, C, ldc, m, n);
+  const bool alias_a = overlaps(a.A, a.lda, TA ? k : m, TA ? m : k, a.C, a.ldc, m, n);
+  const bool alias_b = overlaps(a.B, a.ldb, TB ? n : k, TB ? k : n, a.C, a.ldc, m, n);
   if (alias_a || alias_b) {
-    if (MODE == 3 || MODE == 4 || t_bz) return SMG_ERR_ARG;  // (the symbolic step's products never alias)
-    if (MODE == 0 && alias_a && !alias_b && n <= 64)
-      return launch<32, 64, 32, TA, TB, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
-    if (MODE == 0 && alias_b && !alias_a && m <= 64)
-      return launch<64, 32, 32, TA, TB, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
-    // general aliasing: out of place through a workspace, then C = T (+ beta C)
+    // (the symbolic step's products never alias; neither does one with a
+    // beta-zero boundary or a second output: both are refused, not dropped)
+    if (MODE == 3 || MODE == 4 || a.bz || a.C2) return SMG_ERR_ARG;
+    if (MODE == 0 && alias_a && !alias_b && n <= 64) return launch<32, 64, 32, TA, TB, 0>(ctx, a);
+    if (MODE == 0 && alias_b && !alias_a && m <= 64) return launch<64, 32, 32, TA, TB, 0>(ctx, a);
+    // general aliasing: out of place through a workspace, then C = T (+ beta C).
+    // The product into T keeps the triangles and the K cuts (they describe the
+    // operands) and has no beta-zero boundary (bz is 0 here, and beta is).
     double* T = smg_ws(ctx, SMG_WS_ALIAS, (size_t)m * n);
     if (!T) return SMG_ERR_OOM;
-    int rc = dispatch_tile<TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, 0.0, T, m, tri, true);
+    gemm_args t = a;
+    t.beta = 0.0, t.C = T, t.ldc = m, t.bz = 0;
+    int rc = dispatch_tile<TA, TB, MODE>(ctx, t, true);
     if (rc) return rc;
-    if (beta == 0.0) return smg_copy_impl(ctx, m, n, T, m, C, ldc, 1.0, 0);
-    if (beta != 1.0) {
-      rc = smg_scale_impl(ctx, m, n, beta, C, ldc, MODE);
+    if (a.beta == 0.0) return smg_copy_impl(ctx, m, n, T, m, a.C, a.ldc, 1.0, 0);
+    if (a.beta != 1.0) {
+      rc = smg_scale_impl(ctx, m, n, a.beta, a.C, a.ldc, MODE);
       if (rc) return rc;
     }
-    return smg_copy_impl(ctx, m, n, T, m, C, ldc, 1.0, 1);
+    return smg_copy_impl(ctx, m, n, T, m, a.C, a.ldc, 1.0, 1);
   }
   // tile size by how many CUs the output grid can occupy (256 CUs): large
   // outputs take 128x128 tiles (operand reuse), mid-size 64x64, and the
@@ -883,12 +706,10 @@ int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double*
     const bool policy = (SMG_GEMM_DMA_FAMILIES & fam) && k >= 512 && !(g128 && !tri) &&
                         (mid_tiles >= 256 || (mid_tiles >= SMG_GEMM_DMA_MIN_TILES && k <= 1024));
     const bool want = ctx->gemm_stage == 2 || (ctx->gemm_stage == 0 && policy);
-    if (want && !aliased && dma_eligible(m, n, k, A, lda, B, ldb, C, ldc)) {
+    if (want && !aliased && dma_eligible(m, n, k, a.A, a.lda, a.B, a.ldb, a.C, a.ldc)) {
       if (mid_tiles <= SMG_GEMM_DMA_KS2_MAX)
-        return launch<64, 64, SMG_GEMM_DMA_BK2, TA, TB, MODE, 2, SMG_GEMM_DMA_NB2>(ctx, m, n, k, alpha, A, lda, B, ldb,
-                                                                                 beta, C, ldc, 1, 0, 0, 0, tri);
-      return launch<64, 64, SMG_GEMM_DMA_BK1, TA, TB, MODE, 1, SMG_GEMM_DMA_NB1>(ctx, m, n, k, alpha, A, lda, B, ldb,
-                                                                               beta, C, ldc, 1, 0, 0, 0, tri);
+        return launch<64, 64, SMG_GEMM_DMA_BK2, TA, TB, MODE, 2, SMG_GEMM_DMA_NB2>(ctx, a);
+      return launch<64, 64, SMG_GEMM_DMA_BK1, TA, TB, MODE, 1, SMG_GEMM_DMA_NB1>(ctx, a);
     }
   }
   // (triangle modes keep 64 x 64 tiles: half the 128-tile grid would sit on
@@ -900,13 +721,13 @@ int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double*
   // inverse doubling ran at 27 TF/s -- so those need 4 per CU to balance,
   // else the 64 x 64 grid's longest-K-first order takes them)
   if (FULLC && big_tiles >= (tri ? SMG_GEMM_TRI128_MIN : 256) && k > 128)
-    return launch<128, 128, 16, TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
+    return launch<128, 128, 16, TA, TB, MODE>(ctx, a);
   // long-K transposed-A products with a small output (the Murray reverse's
   // [R_adj | D_adj] -= C_adj^T [B | C]: 512 x K x m, m >= 1536): 128 x 64
   // tiles split over K (tools/ubench_gemm: (512,2048,2048) 87 vs 100 us,
   // (512,1024,3072) 68 vs 81 us with 32 x 32)
   if (MODE == 0 && TA && !TB && k >= 1536 && mid_tiles < 512)
-    return launch<128, 64, 16, TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
+    return launch<128, 64, 16, TA, TB, MODE>(ctx, a);
   // 64 x 64 tiles from 256 tiles on (one per CU), with 8 waves (KS = 2: the
   // two wave groups split every K stage) up to ~6 tiles per CU; 32 x 32
   // below that (4x the workgroups), and for the tall NN products with
@@ -918,19 +739,39 @@ int dispatch_tile(smg_ctx* ctx, int m, int n, int k, double alpha, const double*
   //   (512,512,512) 11.5 (32x32) / 10.2 (32x32 KS=2)
   // (and a 64 x 64 grid below 256 tiles, split over K or not, loses to 32 x 32:
   // (3584,256,256) 18.6 vs 28 us)
-  if (mid_tiles >= 512) {
-    if (mid_tiles <= SMG_GEMM_KS2_MAX)
-      return launch<64, 64, BK64, TA, TB, MODE, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
-    return launch<64, 64, BK64, TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
-  }
   const bool tall_nn = MODE == 0 && !TA && !TB && n <= 512;
-  if (mid_tiles >= 256 && !tall_nn)
-    return launch<64, 64, BK64, TA, TB, MODE, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
+  if (mid_tiles >= 512 ? mid_tiles <= SMG_GEMM_KS2_MAX : (mid_tiles >= 256 && !tall_nn))
+    return launch<64, 64, BK64, TA, TB, MODE, 2>(ctx, a);
+  if (mid_tiles >= 512) return launch<64, 64, BK64, TA, TB, MODE>(ctx, a);
   const long long t32 = smg_ceil_div(m, 32);
   const long long small_tiles = (!FULLC && m == n) ? t32 * (t32 + 1) / 2 : t32 * smg_ceil_div(n, 32);
-  if (small_tiles <= 256)
-    return launch<32, 32, 32, TA, TB, MODE, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
-  return launch<32, 32, 32, TA, TB, MODE>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, 0, 0, tri);
+  if (small_tiles <= 256) return launch<32, 32, 32, TA, TB, MODE, 2>(ctx, a);
+  return launch<32, 32, 32, TA, TB, MODE>(ctx, a);
+}
+
+// The one map from (ta, tb, mode) to the template arguments.  mode 0 to 4:
+// k_gemm's MODE, the tile by dispatch_tile; BATCHED: the batched entry (full
+// C, operands that do not alias), 64 x 64 tiles from 192 of them on, else 32 x 32.
+constexpr int BATCHED = -1;
+int dispatch(smg_ctx* ctx, int ta, int tb, int mode, const gemm_args& a) {
+  auto go = [&](auto TA, auto TB) {
+    constexpr bool ta_ = decltype(TA)::value, tb_ = decltype(TB)::value;
+    switch (mode) {
+      case BATCHED:
+        if ((long long)smg_ceil_div(a.m, 64) * smg_ceil_div(a.n, 64) * a.batch >= 192)
+          return launch<64, 64, BK64, ta_, tb_, 0>(ctx, a);
+        return launch<32, 32, 32, ta_, tb_, 0>(ctx, a);
+      case 1: return dispatch_tile<ta_, tb_, 1>(ctx, a);
+      case 2: return dispatch_tile<ta_, tb_, 2>(ctx, a);
+      case 3: return dispatch_tile<ta_, tb_, 3>(ctx, a);
+      case 4: return dispatch_tile<ta_, tb_, 4>(ctx, a);
+      default: return dispatch_tile<ta_, tb_, 0>(ctx, a);
+    }
+  };
+  if (!ta && !tb) return go(std::false_type{}, std::false_type{});
+  if (!ta && tb) return go(std::false_type{}, std::true_type{});
+  if (ta && !tb) return go(std::true_type{}, std::false_type{});
+  return go(std::true_type{}, std::true_type{});
 }
 
 }  // namespace
@@ -944,57 +785,15 @@ int smg_gemm_batched_impl(smg_ctx* ctx, int ta, int tb, int m, int n, int k, dou
   if (k <= 0 || alpha == 0.0) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GEMM);
   if (ctx->prof_on) ctx->prof_flops[SMG_FAM_GEMM] += 2.0 * m * n * k * batch;
-  const bool big = (long long)smg_ceil_div(m, 64) * smg_ceil_div(n, 64) * batch >= 192;
-#define SMG_BATCHED(TA_, TB_)                                                                    \
-  return big ? launch<64, 64, BK64, TA_, TB_, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, \
-                                               batch, sA, sB, sC)                                 \
-             : launch<32, 32, 32, TA_, TB_, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, \
-                                               batch, sA, sB, sC);
-  if (!ta && !tb) SMG_BATCHED(false, false)
-  if (!ta && tb) SMG_BATCHED(false, true)
-  if (ta && !tb) SMG_BATCHED(true, false)
-  SMG_BATCHED(true, true)
-#undef SMG_BATCHED
+  gemm_args a = {m, n, k, alpha, A, lda, B, ldb, beta, C, ldc};
+  a.batch = batch, a.sA = sA, a.sB = sB, a.sC = sC;
+  return dispatch(ctx, ta, tb, BATCHED, a);
 }
 
 int smg_gemm_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int k,
                   double alpha, const double* A, int lda, const double* B, int ldb,
                   double beta, double* C, int ldc, int tri) {
-  if (m <= 0 || n <= 0) return SMG_OK;
-  if (k <= 0 || alpha == 0.0) {
-    if (beta == 1.0) return SMG_OK;
-    return smg_scale_impl(ctx, m, n, beta, C, ldc, uplo);
-  }
-  smg_prof_scope prof(ctx, SMG_FAM_GEMM);
-  if (ctx->prof_on) {
-    // the K cuts of triangular operands execute about half (one) or a third
-    // (two, as in V V^T with a triangle output) of the dense count
-    const double cut = (tri & 3) && (tri & 12) ? 1.0 / 3.0 : (tri ? 0.5 : 1.0);
-    ctx->prof_flops[SMG_FAM_GEMM] +=
-        cut * (uplo ? 2.0 * k * ((double)m * n - (double)n * (n - 1) / 2) : 2.0 * m * n * k);
-  }
-  if (uplo == 1) {
-    if (!ta && tb) return dispatch_tile<false, true, 1>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (ta && !tb) return dispatch_tile<true, false, 1>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (!ta && !tb) return dispatch_tile<false, false, 1>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    return dispatch_tile<true, true, 1>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  }
-  if (uplo == 3) {  // lower half computed, stored mirrored (symmetric C)
-    if (ta && !tb) return dispatch_tile<true, false, 3>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (!ta && !tb) return dispatch_tile<false, false, 3>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (!ta && tb) return dispatch_tile<false, true, 3>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    return dispatch_tile<true, true, 3>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  }
-  if (uplo == 2) {
-    if (!ta && tb) return dispatch_tile<false, true, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (ta && !tb) return dispatch_tile<true, false, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    if (!ta && !tb) return dispatch_tile<false, false, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-    return dispatch_tile<true, true, 2>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  }
-  if (!ta && !tb) return dispatch_tile<false, false, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  if (!ta && tb) return dispatch_tile<false, true, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  if (ta && !tb) return dispatch_tile<true, false, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  return dispatch_tile<true, true, 0>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
+  return smg_gemm_cut_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri, 0, -1, -1);
 }
 
 // smg_gemm_impl with beta taken as 0 for C's rows from bz on (bz > 0) or its
@@ -1015,13 +814,23 @@ int smg_gemm_cut_impl(smg_ctx* ctx, int ta, int tb, int uplo, int m, int n, int 
                       int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri, int bz, int cut_a,
                       int cut_b) {
   if (bz % 128 || cut_a < -1 || cut_b < -1) return SMG_ERR_ARG;
-  t_bz = bz;
-  t_cut_a = cut_a;
-  t_cut_b = cut_b;
-  const int rc = smg_gemm_impl(ctx, ta, tb, uplo, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  t_bz = 0;
-  t_cut_a = t_cut_b = -1;
-  return rc;
+  if (m <= 0 || n <= 0) return SMG_OK;
+  if (k <= 0 || alpha == 0.0) {
+    if (beta == 1.0) return SMG_OK;
+    return smg_scale_impl(ctx, m, n, beta, C, ldc, uplo);
+  }
+  smg_prof_scope prof(ctx, SMG_FAM_GEMM);
+  if (ctx->prof_on) {
+    // the K cuts of triangular operands execute about half (one) or a third
+    // (two, as in V V^T with a triangle output) of the dense count
+    const double cut = (tri & 3) && (tri & 12) ? 1.0 / 3.0 : (tri ? 0.5 : 1.0);
+    ctx->prof_flops[SMG_FAM_GEMM] +=
+        cut * (uplo ? 2.0 * k * ((double)m * n - (double)n * (n - 1) / 2) : 2.0 * m * n * k);
+  }
+  gemm_args a = {m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri};
+  a.bz = bz, a.cut_a = cut_a, a.cut_b = cut_b;
+  // uplo 1 / 2: the lower / upper triangle of C; 3: the lower half computed, stored mirrored (symmetric C)
+  return dispatch(ctx, ta, tb, uplo >= 1 && uplo <= 3 ? uplo : 0, a);
 }
 
 // C = alpha op(A) op(B) + beta C (full) and C2 = tril(C) with halved diagonal
@@ -1031,15 +840,9 @@ int smg_gemm_dual_impl(smg_ctx* ctx, int ta, int tb, int m, int n, int k, double
   if (k <= 0 || alpha == 0.0 || !C2) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GEMM);
   if (ctx->prof_on) ctx->prof_flops[SMG_FAM_GEMM] += 2.0 * m * n * k;
-  t_c2 = C2;
-  t_ldc2 = ldc2;
-  int rc;
-  if (!ta && !tb) rc = dispatch_tile<false, false, 4>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else if (ta && !tb) rc = dispatch_tile<true, false, 4>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else if (!ta && tb) rc = dispatch_tile<false, true, 4>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else rc = dispatch_tile<true, true, 4>(ctx, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  t_c2 = nullptr;
-  return rc;
+  gemm_args a = {m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri};
+  a.C2 = C2, a.ldc2 = ldc2;
+  return dispatch(ctx, ta, tb, 4, a);
 }
 
 // C = alpha op(A) op(B) + beta C, symmetric: its lower triangle computed and
@@ -1056,15 +859,9 @@ int smg_gemm_sym_phi_impl(smg_ctx* ctx, int ta, int tb, int n, int k, double alp
     const double cut = (tri & 3) && (tri & 12) ? 1.0 / 3.0 : (tri ? 0.5 : 1.0);
     ctx->prof_flops[SMG_FAM_GEMM] += cut * 2.0 * k * ((double)n * n - (double)n * (n - 1) / 2);
   }
-  t_c2 = P;
-  t_ldc2 = ldp;
-  int rc;
-  if (!ta && !tb) rc = dispatch_tile<false, false, 3>(ctx, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else if (ta && !tb) rc = dispatch_tile<true, false, 3>(ctx, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else if (!ta && tb) rc = dispatch_tile<false, true, 3>(ctx, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  else rc = dispatch_tile<true, true, 3>(ctx, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri);
-  t_c2 = nullptr;
-  return rc;
+  gemm_args a = {n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, tri};
+  a.C2 = P, a.ldc2 = ldp;
+  return dispatch(ctx, ta, tb, 3, a);
 }
 
 extern "C" int smg_gemm_tri(smg_ctx* ctx, int ta, int tb, int uplo, int tri, int m, int n, int k,
