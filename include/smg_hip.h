@@ -266,6 +266,24 @@ int smg_gp_cov_fwd(smg_ctx* ctx, int family, const double* x, int D, int n, doub
  * sums.  smg_gp_exp_quad_cov_nd_rev is this entry with SMG_GP_EXP_QUAD. */
 int smg_gp_cov_rev(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l,
                    const double* Kadj, int ldka, double* out2);
+/* The cross-covariance between two point sets, the (x1, x2, sigma,
+ * length_scale) overloads of the same four functions (prim/mat/fun/):
+ * K (n1 x n2, column-major, ld ldk >= n1): K_ij = k_family(x1_i, x2_j); x1 is
+ * D x n1, x2 is D x n2, point-major as smg_gp_cov_fwd's x (D <= 8192).  No
+ * diagonal: a coincident pair comes out of the family's expression (exactly
+ * sigma^2, and a zero l-derivative), and x1 == x2 gives the bits of
+ * smg_gp_cov_fwd.  Rows n1 .. ldk - 1 are not written.  A workgroup takes a
+ * column of K, and a part of its rows when there are few columns, so either
+ * set may be the larger one.  SMG_ERR_ARG for an unknown family, a null
+ * pointer, D < 1 or ldk < n1; n1 == 0 or n2 == 0 is a no-op. */
+int smg_gp_cross_cov_fwd(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
+                         double sigma, double l, double* K, int ldk);
+/* out2[0] += 2 sum_ij Kadj_ij K_ij / sigma,
+ * out2[1] += sum_ij Kadj_ij dK_ij/dl            (every position once)
+ * from the adjoint Kadj (n1 x n2, ld ldka >= n1); K is recomputed from the
+ * points, fixed-order sums (the same bits run to run). */
+int smg_gp_cross_cov_rev(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
+                         double sigma, double l, const double* Kadj, int ldka, double* out2);
 
 /* Tangent of the same covariance along (sigma', l') -- what the fvar<var>
  * instantiation of gp_exp_quad_cov computes inside hessian_times_vector
@@ -704,6 +722,16 @@ int smg_gp_ard_scale(smg_ctx* ctx, const double* x, int D, int n, const double* 
  * K_ij recomputed from zt with smg_gp_cov_fwd's per-element expression. */
 int smg_gp_ard_cov_rev(smg_ctx* ctx, int family, const double* zt, int D, int n, double sigma, const double* l,
                        const double* Kadj, int ldka, double* out);
+/* The cross-covariance's reverse for ARD (its forward: smg_gp_ard_scale on
+ * both sets, then smg_gp_cross_cov_fwd with l = 1.0).  z1t (n1 x D) and z2t
+ * (n2 x D) are the coordinate-major scaled points smg_gp_ard_scale writes;
+ * out (1 + D doubles, accumulated into), every position once, no diagonal:
+ *   out[0]     += 2 sum_ij Kadj_ij K_ij / sigma
+ *   out[1 + d] += sum_ij Kadj_ij sigma^2 h(a) t_d^2 / l_d,  t_d = z1_id - z2_jd
+ * l: a host array of D doubles, 1 <= D <= SMG_GP_ARD_MAX_D.  Argument checks
+ * as smg_gp_cross_cov_rev. */
+int smg_gp_ard_cross_cov_rev(smg_ctx* ctx, int family, const double* z1t, int n1, const double* z2t, int n2, int D,
+                             double sigma, const double* l, const double* Kadj, int ldka, double* out);
 /* smg_gp_cov_inverse_adjoint_x for ARD: G = adj Phi(sum_o s_o s_o^T - k C)
  * over C's lower triangle, dadj = sum_i G_ii, out (1 + D doubles) = the sums
  * above with G for Kadj.  Written, not accumulated; either may be NULL, and

@@ -15,7 +15,9 @@
 // The forward and reverse kernels are templated on the covariance family
 // (gp_family.h: exp_quad, exponential, Matern 3/2 and 5/2); their argument
 // inv_half_sq_l is the family's length-scale coefficient, 1 / (2 l^2) for
-// exp_quad.  The tangent kernels are exp_quad's alone.
+// exp_quad.  The tangent kernels are exp_quad's alone.  The cross-covariance
+// K(x1, x2) (smg_gp_cross_cov_fwd / _rev) is the same walk over a rectangle,
+// without the diagonal.
 //
 // add_diag: prim/mat/fun/add_diag.hpp:20-55.
 #include "smg_internal.h"
@@ -584,6 +586,213 @@ int gp_chol_src(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl) {
   return SMG_OK;
 }
 
+// Cross-covariance K(x1, x2), n1 x n2 (smg_gp_cross_cov_fwd / _rev): the walk
+// of k_gp_fwd_col2 / k_gp_nd_fwd over a rectangle.  A workgroup walks whole
+// columns j (x2_j in a register for D == 1, staged in LDS otherwise), its
+// lanes consecutive rows i of x1.  No diagonal branch: every element is the
+// family's expression of x1_i - x2_j, which is s2 exactly at a coincident
+// pair and, the difference's sign dropping out of from_diff / from_sq, the
+// bits of k_gp_fwd* when x1 == x2.  The grid's y dimension splits the rows
+// (blockIdx.y takes every gridDim.y-th pass of a workgroup's rows), so that a
+// tall K with few columns still fills the chip; it is 1 once the columns
+// alone give GP_BLOCKS workgroups (cross_grid).
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_cross_fwd_col2(const double* __restrict__ x1, int n1,
+                                                           const double* __restrict__ x2, int n2, double s2,
+                                                           double c, double* __restrict__ K, int ldk) {
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          const double2 xi = xr[p];
+          double2 v;
+          v.x = gp_fam<F>::k(gp_fam<F>::from_diff(xi.x - xj), s2, c);
+          v.y = gp_fam<F>::k(gp_fam<F>::from_diff(xi.y - xj), s2, c);
+          col[p] = v;
+        }
+      }
+    }
+  }
+}
+
+// Generic form: any n1 and ldk (rows n1 .. ldk - 1 are not written)
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_cross_fwd(const double* __restrict__ x1, int n1,
+                                                      const double* __restrict__ x2, int n2, double s2, double c,
+                                                      double* __restrict__ K, int ldk) {
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double* col = K + (size_t)j * ldk;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256)
+      col[i] = gp_fam<F>::k(gp_fam<F>::from_diff(x1[i] - xj), s2, c);
+  }
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_cross_nd_fwd(const double* __restrict__ x1, int n1,
+                                                         const double* __restrict__ x2, int n2, int D, double s2,
+                                                         double c, double* __restrict__ K, int ldk) {
+  extern __shared__ double xj[];
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double* xi = x1 + (size_t)i * D;
+      double d2 = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double t = xi[d] - xj[d];
+        d2 += t * t;
+      }
+      K[i + (size_t)j * ldk] = gp_fam<F>::k(gp_fam<F>::from_sq(d2), s2, c);
+    }
+  }
+}
+
+// The reverse's per-workgroup partials [sum Kadj K, l-scaled sum Kadj dK/dl]
+// over the same walks (one read of Kadj, K recomputed); k_gp_rev_final sums them.
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_cross_rev_partials_col2(const double* __restrict__ x1, int n1,
+                                                                    const double* __restrict__ x2, int n2,
+                                                                    double s2, double c,
+                                                                    const double* __restrict__ Ka, int lda,
+                                                                    double* __restrict__ part) {
+  __shared__ double lds[16];
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  double al = 0.0, as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+      double2 a[4], xi[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          a[k] = col[p];
+          xi[k] = xr[p];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          gp_fam<F>::acc(a[k].x, gp_fam<F>::from_diff(xi[k].x - xj), s2, c, as, al);
+          gp_fam<F>::acc(a[k].y, gp_fam<F>::from_diff(xi[k].y - xj), s2, c, as, al);
+        }
+      }
+    }
+  }
+  const double sl = block_sum(al, lds);
+  __syncthreads();
+  const double ss = block_sum(as, lds);
+  if (threadIdx.x == 0) {
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    part[2 * b + 0] = ss;
+    part[2 * b + 1] = sl;
+  }
+}
+
+// Generic form, D >= 1 (x2_j staged in LDS as k_gp_cross_nd_fwd does; D == 1 from the difference)
+template <int F>
+__global__ __launch_bounds__(256) void k_gp_cross_rev_partials(const double* __restrict__ x1, int n1,
+                                                               const double* __restrict__ x2, int n2, int D,
+                                                               double s2, double c, const double* __restrict__ Ka,
+                                                               int lda, double* __restrict__ part) {
+  extern __shared__ double xj[];
+  __shared__ double lds[16];
+  double al = 0.0, as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    const double* col = Ka + (size_t)j * lda;
+    const double xj0 = xj[0];
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double a = col[i];
+      if (D == 1) {
+        gp_fam<F>::acc(a, gp_fam<F>::from_diff(x1[i] - xj0), s2, c, as, al);
+      } else {
+        const double* xi = x1 + (size_t)i * D;
+        double d2 = 0.0;
+        for (int d = 0; d < D; ++d) {
+          const double t = xi[d] - xj[d];
+          d2 += t * t;
+        }
+        gp_fam<F>::acc(a, gp_fam<F>::from_sq(d2), s2, c, as, al);
+      }
+    }
+  }
+  const double sl = block_sum(al, lds);
+  __syncthreads();
+  const double ss = block_sum(as, lds);
+  if (threadIdx.x == 0) {
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    part[2 * b + 0] = ss;
+    part[2 * b + 1] = sl;
+  }
+}
+
+// One workgroup per column up to GP_BLOCKS (the column loop wraps beyond),
+// times as many row parts as bring the grid to about GP_BLOCKS workgroups, none
+// of them without rows; rows: what a workgroup covers in one pass.
+inline dim3 cross_grid(int n1, int n2, int rows) {
+  const int gx = n2 < GP_BLOCKS ? n2 : GP_BLOCKS;
+  int gy = smg_ceil_div(n1, rows);
+  if (gy > GP_BLOCKS / gx) gy = GP_BLOCKS / gx;
+  return dim3(gx, gy < 1 ? 1 : gy);
+}
+
+// K(x1, x2) of family F for checked arguments, n1, n2 > 0
+template <int F>
+int gp_cross_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma, double l,
+                 double* K, int ldk) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma;
+  const double c = gp_fam<F>::coef(l);
+  if (D > 1)
+    hipLaunchKernelGGL(k_gp_cross_nd_fwd<F>, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1,
+                       x2, n2, D, s2, c, K, ldk);
+  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
+    hipLaunchKernelGGL(k_gp_cross_fwd_col2<F>, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2,
+                       c, K, ldk);
+  else
+    hipLaunchKernelGGL(k_gp_cross_fwd<F>, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, c, K,
+                       ldk);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// out2 += [d/dsigma, d/dl] of K(x1, x2) from its adjoint (same forms)
+template <int F>
+int gp_cross_rev(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma, double l,
+                 const double* Kadj, int ldka, double* out2) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma;
+  const double c = gp_fam<F>::coef(l);
+  const bool col2 = D == 1 && col2_ok(x1, 2, n1) && col2_ok(Kadj, ldka, n1);
+  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
+  const int nb = (int)(grid.x * grid.y);
+  double* part = smg_ws(ctx, SMG_WS_RED, 2 * (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  if (col2)
+    hipLaunchKernelGGL(k_gp_cross_rev_partials_col2<F>, grid, dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, c, Kadj,
+                       ldka, part);
+  else
+    hipLaunchKernelGGL(k_gp_cross_rev_partials<F>, grid, dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2, n2, D,
+                       s2, c, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_rev_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
 }  // namespace
 
 bool smg_gp_source_ok(const smg_gp_source* s) {
@@ -657,6 +866,35 @@ int smg_gp_cov_rev(smg_ctx* ctx, int family, const double* x, int D, int n, doub
     case SMG_GP_MATERN32: return gp_rev<SMG_GP_MATERN32>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
     case SMG_GP_MATERN52: return gp_rev<SMG_GP_MATERN52>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
     default: return gp_rev<SMG_GP_EXP_QUAD>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
+  }
+}
+
+int smg_gp_cross_cov_fwd(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
+                         double sigma, double l, double* K, int ldk) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL: return gp_cross_fwd<SMG_GP_EXPONENTIAL>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
+    case SMG_GP_MATERN32: return gp_cross_fwd<SMG_GP_MATERN32>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
+    case SMG_GP_MATERN52: return gp_cross_fwd<SMG_GP_MATERN52>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
+    default: return gp_cross_fwd<SMG_GP_EXP_QUAD>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
+  }
+}
+
+int smg_gp_cross_cov_rev(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
+                         double sigma, double l, const double* Kadj, int ldka, double* out2) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
+  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!x1 || !x2 || !Kadj || !out2 || ldka < n1) return SMG_ERR_ARG;
+  switch (family) {
+    case SMG_GP_EXPONENTIAL:
+      return gp_cross_rev<SMG_GP_EXPONENTIAL>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
+    case SMG_GP_MATERN32: return gp_cross_rev<SMG_GP_MATERN32>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
+    case SMG_GP_MATERN52: return gp_cross_rev<SMG_GP_MATERN52>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
+    default: return gp_cross_rev<SMG_GP_EXP_QUAD>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
   }
 }
 

@@ -9,6 +9,8 @@
 //   tril(K + d I) -> L      smg_gp_source {x = z, l = 1}                        (gp.hip, unchanged)
 //   sigma', l_1' .. l_D'    smg_gp_ard_cov_rev (dense adjoint) and
 //                           smg_gp_ard_cov_inverse_adjoint (G from K^{-1})      (this file)
+//   the same sums of the    smg_gp_ard_cross_cov_rev (dense adjoint, z1 and z2
+//   cross-covariance        scaled by the same l)                               (this file)
 // With t_d = z_id - z_jd, r^2 = sum_d t_d^2 in coordinate order and h from
 // gp_family.h:  dK_ij/dl_d = sigma^2 h t_d^2 / l_d (i != j), nothing on the
 // diagonal.  K_ij is recomputed with the forward's expression
@@ -243,6 +245,41 @@ void launch_inv(smg_ctx* ctx, int nb, const double* C, int ldc, int n, const dou
                        s2, c, d0, part);
 }
 
+// k_gp_ard_rev_partials for the cross-covariance K(x1, x2), n1 x n2: the
+// column point from z2t, the row points from z1t, no diagonal (a coincident
+// pair goes through ard_terms: K = s2, t_d = 0, and exponential's h is 0 there).
+// blockIdx.y takes every gridDim.y-th pass of the rows (a tall K with few
+// columns); its partials follow those of the row parts before it.
+template <int F, int DP>
+__global__ __launch_bounds__(256) void k_gp_ard_cross_rev_partials(const double* __restrict__ z1t, int n1,
+                                                                   const double* __restrict__ z2t, int n2, int D,
+                                                                   double s2, double c, int d0,
+                                                                   const double* __restrict__ Ka, int lda,
+                                                                   double* __restrict__ part) {
+  __shared__ double zj[SMG_GP_ARD_MAX_D];
+  double sa = 0.0, al[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) al[d] = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    if ((int)threadIdx.x < D) zj[threadIdx.x] = z2t[(size_t)threadIdx.x * n2 + j];
+    __syncthreads();
+    const double* col = Ka + (size_t)j * lda;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256)
+      ard_terms<F, DP>(z1t + i, n1, zj, D, d0, col[i], s2, c, sa, al);
+  }
+  ard_block_partials<DP>(0.0, sa, al, D, d0, part + (size_t)(D + 2) * gridDim.x * blockIdx.y);
+}
+
+template <int F, int DP>
+void launch_cross_rev(smg_ctx* ctx, dim3 grid, const double* z1t, int n1, const double* z2t, int n2, int D, double s2,
+                      const double* Ka, int lda, double* part) {
+  const double c = gp_fam<F>::coef(1.0);
+  for (int d0 = 0; d0 < D; d0 += DP)
+    hipLaunchKernelGGL((k_gp_ard_cross_rev_partials<F, DP>), grid, dim3(256), 0, ctx->stream, z1t, n1, z2t, n2, D,
+                       s2, c, d0, Ka, lda, part);
+}
+
 // the padded D's register form: 4, 8 or 16 accumulators (16 per pass beyond)
 #define ARD_DISPATCH_DP(FN, F, ...)                \
   do {                                             \
@@ -287,6 +324,27 @@ int smg_gp_ard_cov_rev(smg_ctx* ctx, int family, const double* zt, int D, int n,
   double* part = smg_ws(ctx, SMG_WS_RED, (size_t)(D + 2) * nb);
   if (!part) return SMG_ERR_OOM;
   ARD_DISPATCH(launch_rev, ctx, nb, zt, D, n, sigma * sigma, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_ard_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, D, 1.0, sigma, host_scales(l, D),
+                     1, (double*)nullptr, out);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+int smg_gp_ard_cross_cov_rev(smg_ctx* ctx, int family, const double* z1t, int n1, const double* z2t, int n2, int D,
+                             double sigma, const double* l, const double* Kadj, int ldka, double* out) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > SMG_GP_ARD_MAX_D || !family_ok(family)) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!z1t || !z2t || !l || !Kadj || !out || ldka < n1) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  // one workgroup per column, times row parts up to about 2048 workgroups (gp.hip's cross_grid)
+  const int gx = n2 < 2048 ? n2 : 2048;
+  int gy = (n1 + 255) / 256;
+  if (gy > 2048 / gx) gy = 2048 / gx;
+  const dim3 grid(gx, gy);
+  const int nb = gx * gy;
+  double* part = smg_ws(ctx, SMG_WS_RED, (size_t)(D + 2) * nb);
+  if (!part) return SMG_ERR_OOM;
+  ARD_DISPATCH(launch_cross_rev, ctx, grid, z1t, n1, z2t, n2, D, sigma * sigma, Kadj, ldka, part);
   hipLaunchKernelGGL(k_gp_ard_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, D, 1.0, sigma, host_scales(l, D),
                      1, (double*)nullptr, out);
   SMG_LAUNCH_CHECK();

@@ -128,6 +128,10 @@ _SIGS = {
     "smg_gp_ard_scale": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "smg_gp_ard_cov_rev": (_I, [_P, _I, _P, _I, _I, _D, _P, _P, _I, _P]),
     "smg_gp_ard_cov_inverse_adjoint": (_I, [_P, _I, _P, _I, _I, _P, _I, _L, _D, _P, _I, _D, _P, _P, _P]),
+    # cross-covariance K(x1, x2): (ctx, family, x1, n1, x2, n2, D, sigma, l | host l, ...)
+    "smg_gp_cross_cov_fwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _D, _P, _I]),
+    "smg_gp_cross_cov_rev": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _D, _P, _I, _P]),
+    "smg_gp_ard_cross_cov_rev": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _P, _P, _I, _P]),
     "smg_log_sum_exp_fwd": (_I, [_P, _P, _L, _P]),
     "smg_log_sum_exp_rev": (_I, [_P, _P, _L, _D, _D, _P]),
     "smg_lgamma_fwd": (_I, [_P, _P, _L, _P]),

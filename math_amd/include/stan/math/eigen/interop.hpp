@@ -39,6 +39,7 @@
 #include <stan/math/rev/fun/gp_exp_quad_cov.hpp>
 #include <stan/math/rev/fun/gp_matern_cov.hpp>
 #include <stan/math/rev/fun/gp_ard_cov.hpp>
+#include <stan/math/rev/fun/gp_cross_cov.hpp>
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
@@ -947,6 +948,139 @@ STAN_MATH_AMD_GP_ARD_OVERLOADS(gp_matern32_cov, SMG_GP_MATERN32)
 STAN_MATH_AMD_GP_ARD_OVERLOADS(gp_matern52_cov, SMG_GP_MATERN52)
 
 #undef STAN_MATH_AMD_GP_ARD_OVERLOADS
+
+// ---- cross-covariance (x1, x2) over D-dimensional points (rev/fun/gp_cross_cov.hpp)
+namespace internal {
+/** Every entry of one set not NaN under `name` ("x1" / "x2"); indexed:
+ * gp_exp_quad_cov's wording, the index within the point ("x1[<d + 1>]"). */
+template <typename T_x>
+inline void gp_cross_check_points_not_nan(const char* fn, const char* name, const std::vector<T_x>& x, bool indexed) {
+  for (size_t i = 0; i < x.size(); ++i)
+    for (int d = 0; d < int(x[i].size()); ++d)
+      if (std::isnan(x[i](d))) {
+        if (!indexed) gp_cross_throw_nan(fn, name);
+        std::ostringstream m;
+        m << fn << ": " << name << "[" << d + 1 << "] is nan, but must not be nan!";
+        throw std::domain_error(m.str());
+      }
+}
+/** The points' dimension (the first point's, of x1 or else of x2; 1 without
+ * points) after the first size mismatch squared_distance meets, x1 then x2. */
+template <typename T_x>
+inline int gp_cross_points_dim(const std::vector<T_x>& x1, const std::vector<T_x>& x2) {
+  const int D = !x1.empty() ? int(x1[0].size()) : !x2.empty() ? int(x2[0].size()) : 1;
+  for (const std::vector<T_x>* x : {&x1, &x2})
+    for (size_t i = 0; i < x->size(); ++i)
+      if (int((*x)[i].size()) != D) {
+        std::ostringstream m;
+        m << "squared_distance: size of v1 (" << (*x)[i].size() << ") and size of v2 (" << D
+          << ") must match in size";
+        throw std::invalid_argument(m.str());
+      }
+  return D;
+}
+/** checked points -> device D x n.  Points without coordinates (D == 0) are
+ * all at distance 0: they go as one coordinate 0 each (1 x n), which gives
+ * K = sigma^2 everywhere and a zero length-scale derivative. */
+template <typename T_x>
+inline dev_data<double> gp_cross_pack_points(const std::vector<T_x>& x, int D) {
+  const size_t n = x.size();
+  if (D == 0) return to_dev_data(std::vector<double>(n, 0.0));
+  std::vector<double> h(n * size_t(D));
+  for (size_t i = 0; i < n; ++i)
+    for (int d = 0; d < D; ++d) h[i * size_t(D) + size_t(d)] = x[i](d);
+  return to_dev_data(h.data(), h.size(), D, int(n));
+}
+
+/** The single-x point forms' order: gp_exp_quad_cov checks the hyperparameters
+ * before the points, the Matern family the points' entries first; the point
+ * sizes come last in both. */
+template <typename T_x>
+inline dev_var_matrix gp_cross_cov_points(int family, const char* fn, const std::vector<T_x>& x1,
+                                          const std::vector<T_x>& x2, double sigma, vari* sigma_vi, double l,
+                                          vari* l_vi) {
+  const bool eq = family == SMG_GP_EXP_QUAD;
+  if (eq) gp_cross_check_hyper(family, fn, sigma, sigma_vi, l, l_vi);
+  gp_cross_check_points_not_nan(fn, "x1", x1, eq);
+  gp_cross_check_points_not_nan(fn, "x2", x2, eq);
+  if (!eq) gp_cross_check_hyper(family, fn, sigma, sigma_vi, l, l_vi);
+  const int D = gp_cross_points_dim(x1, x2);
+  return gp_cross_cov_dev(family, fn, gp_cross_pack_points(x1, D), gp_cross_pack_points(x2, D), D > 0 ? D : 1, sigma,
+                          sigma_vi, l, l_vi);
+}
+/** ARD: gp_ard_cov_points' order (the entries, magnitude, every length scale,
+ * their count, then the point sizes).  Points without coordinates have no
+ * length scale: the one-length-scale node with l = 1 as data. */
+template <typename T_x>
+inline dev_var_matrix gp_ard_cross_cov_points(int family, const char* fn, const std::vector<T_x>& x1,
+                                              const std::vector<T_x>& x2, double sigma, vari* sigma_vi,
+                                              const std::vector<double>& l, const std::vector<vari*>& l_vis) {
+  gp_cross_check_points_not_nan(fn, "x1", x1, false);
+  gp_cross_check_points_not_nan(fn, "x2", x2, false);
+  gp_ard_check_hyper(fn, sigma, l,
+                     !x1.empty() ? size_t(x1[0].size()) : !x2.empty() ? size_t(x2[0].size()) : l.size());
+  const int D = gp_cross_points_dim(x1, x2);
+  if (D == 0)
+    return gp_cross_cov_dev(family, fn, gp_cross_pack_points(x1, 0), gp_cross_pack_points(x2, 0), 1, sigma, sigma_vi,
+                            1.0, nullptr);
+  return gp_ard_cross_cov_dev(family, fn, gp_cross_pack_points(x1, D), gp_cross_pack_points(x2, D), D, sigma,
+                              sigma_vi, l, l_vis);
+}
+}  // namespace internal
+
+// (var, var), (double, var), (var, double) for (sigma, length_scale), and the
+// ARD kinds (var, vector<var>), (double, vector<var>), (var, vector<double>)
+#define STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(FN, FAMILY)                                                      \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const var& sigma,            \
+                           const var& length_scale) {                                                          \
+    return internal::gp_cross_cov_points(FAMILY, #FN, x1, x2, sigma.val(), sigma.vi_, length_scale.val(),      \
+                                         length_scale.vi_);                                                    \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, double sigma,                \
+                           const var& length_scale) {                                                          \
+    return internal::gp_cross_cov_points(FAMILY, #FN, x1, x2, sigma, nullptr, length_scale.val(),              \
+                                         length_scale.vi_);                                                    \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const var& sigma,            \
+                           double length_scale) {                                                              \
+    return internal::gp_cross_cov_points(FAMILY, #FN, x1, x2, sigma.val(), sigma.vi_, length_scale, nullptr);  \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const var& sigma,            \
+                           const std::vector<var>& length_scale) {                                             \
+    return internal::gp_ard_cross_cov_points(FAMILY, #FN, x1, x2, sigma.val(), sigma.vi_,                      \
+                                             internal::gp_ard_values(length_scale),                            \
+                                             internal::gp_ard_varis(length_scale));                            \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, double sigma,                \
+                           const std::vector<var>& length_scale) {                                             \
+    return internal::gp_ard_cross_cov_points(FAMILY, #FN, x1, x2, sigma, nullptr,                              \
+                                             internal::gp_ard_values(length_scale),                            \
+                                             internal::gp_ard_varis(length_scale));                            \
+  }                                                                                                            \
+  template <int R, int C, typename A>                                                                          \
+  inline dev_var_matrix FN(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,                              \
+                           const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const var& sigma,            \
+                           const std::vector<double>& length_scale) {                                          \
+    return internal::gp_ard_cross_cov_points(FAMILY, #FN, x1, x2, sigma.val(), sigma.vi_, length_scale,        \
+                                             std::vector<vari*>());                                            \
+  }
+
+STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_exp_quad_cov, SMG_GP_EXP_QUAD)
+STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_exponential_cov, SMG_GP_EXPONENTIAL)
+STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_matern32_cov, SMG_GP_MATERN32)
+STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_matern52_cov, SMG_GP_MATERN52)
+
+#undef STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS
 
 }  // namespace math
 }  // namespace stan

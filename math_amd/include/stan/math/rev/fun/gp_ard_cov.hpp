@@ -29,8 +29,9 @@
 // them, and for points of unequal sizes (as gp_points_to_device reports it).
 // As for the Matern families these are the reference's messages as recalled;
 // its sources are not part of this repository.
-// Not provided: the cross-covariance (x1, x2) overloads, the fvar<var>
-// tangent, scalar x with a one-element length-scale vector, D > 64.
+// The cross-covariance (x1, x2) overloads are rev/fun/gp_cross_cov.hpp.
+// Not provided: the fvar<var> tangent, scalar x with a one-element
+// length-scale vector, D > 64.
 
 #include <stan/math/rev/fun/gp_matern_cov.hpp>
 

@@ -22,9 +22,9 @@
 // "... must be finite!"), all std::domain_error.  This is the behaviour of
 // the reference's prim templates as recalled; the reference's sources are not
 // part of this repository and the messages could not be compared with them.
-// One length scale per input dimension (ARD) is rev/fun/gp_ard_cov.hpp.
-// Not provided: the cross-covariance (x1, x2) overloads and the fvar<var>
-// tangent.
+// One length scale per input dimension (ARD) is rev/fun/gp_ard_cov.hpp, the
+// cross-covariance (x1, x2) overloads are rev/fun/gp_cross_cov.hpp.
+// Not provided: the fvar<var> tangent.
 
 #include <stan/math/rev/fun/gp_exp_quad_cov.hpp>
 
