@@ -285,6 +285,46 @@ int smg_gp_cross_cov_fwd(smg_ctx* ctx, int family, const double* x1, int n1, con
 int smg_gp_cross_cov_rev(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
                          double sigma, double l, const double* Kadj, int ldka, double* out2);
 
+/* gp_periodic_cov and gp_dot_prod_cov (Stan Math 3.0.0, prim/mat/fun/), square
+ * and cross.  All four entries are rectangular: K (n1 x n2, column-major, ld
+ * ldk >= n1) over x1 (D x n1) and x2 (D x n2), point-major, D in 1 .. 8192; the
+ * square K(x, x) is x1 == x2, n1 == n2.  d_ij as above (|x1_i - x2_j| for
+ * D == 1, else the square root of the squared distance summed in coordinate
+ * order).  They are not members of smg_gp_family: the fused entries
+ * (smg_gp_source, smg_cholesky_fwd_gp_*, smg_gp_cov_inverse_adjoint*) do not
+ * take them.
+ *
+ *   int smg_gp_periodic_cov_fwd(ctx, x1, n1, x2, n2, D, sigma, l, p, K, ldk);
+ *   int smg_gp_periodic_cov_rev(ctx, x1, n1, x2, n2, D, sigma, l, p, Kadj, ldka, out3);
+ *       out3 += [d/dsigma, d/dl, d/dp] of sum(Kadj o K)
+ *   int smg_gp_dot_prod_cov_fwd(ctx, x1, n1, x2, n2, D, sigma, K, ldk);
+ *   int smg_gp_dot_prod_cov_rev(ctx, n1, n2, sigma, Kadj, ldka, out1);
+ *       out1 += 2 sigma sum(Kadj)
+ *
+ * Periodic, with s2 = sigma^2 and a = pi d / p:
+ *   K = s2 exp(-2 sin^2(a) / l^2)       dK/dsigma = 2 K / sigma
+ *   dK/dl = K 4 sin^2(a) / l^3          dK/dp = K (2 pi d / (l^2 p^2)) sin(2a)
+ * sin(a) and cos(a) are sincospi(d (1 / p)), so the argument reduction is
+ * exact.  Every position is computed alike (no diagonal branch, no derivative
+ * divides by d): a coincident pair gives s2 exactly and zero l- and
+ * p-derivatives, and x1 == x2 gives a bitwise symmetric K.
+ * Dot product: K_ij = sigma^2 + sum_d x1_id x2_jd summed in coordinate order,
+ * dK/dsigma = 2 sigma; sigma = 0 is allowed; x1 == x2 is bitwise symmetric.
+ *
+ * Arguments as smg_gp_cross_cov_fwd / _rev: SMG_ERR_ARG for a null ctx, a
+ * negative size, D outside 1 .. 8192, ld < n1 or a null pointer with non-empty
+ * sizes; n1 == 0 or n2 == 0 returns SMG_OK with nothing launched or written.
+ * Rows n1 .. ld - 1 of K are not written and those of Kadj are not read.  The
+ * reverse recomputes K from the points (one read of Kadj), sums per-workgroup
+ * partials in a fixed order (the same bits run to run) and adds to out*. */
+int smg_gp_periodic_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double l, double p, double* K, int ldk);
+int smg_gp_periodic_cov_rev(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double l, double p, const double* Kadj, int ldka, double* out3);
+int smg_gp_dot_prod_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double* K, int ldk);
+int smg_gp_dot_prod_cov_rev(smg_ctx* ctx, int n1, int n2, double sigma, const double* Kadj, int ldka, double* out1);
+
 /* Tangent of the same covariance along (sigma', l') -- what the fvar<var>
  * instantiation of gp_exp_quad_cov computes inside hessian_times_vector
  * (mix/mat/functor/hessian_times_vector.hpp:13-40):

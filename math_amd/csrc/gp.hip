@@ -961,3 +961,385 @@ int smg_add_diag_rev(smg_ctx* ctx, const double* Ba, int ldb, int n, double* Aa,
 }
 
 }  // extern "C"
+
+// gp_periodic_cov and gp_dot_prod_cov (Stan Math 3.0.0, prim/mat/fun/), square
+// and cross: rectangular entries, the square K(x, x) being x1 == x2.  The
+// kernels keep the cross kernels' shape (a workgroup walks whole columns j,
+// x2_j in a register for D == 1 and staged in LDS otherwise, lanes on
+// consecutive rows, the 16-byte form where col2_ok allows, blockIdx.y over the
+// rows by cross_grid) and their reductions (per-workgroup partials in
+// SMG_WS_RED, one ordered pass, no atomics).
+//
+// Periodic, a = pi d / p:  K = s2 exp(-2 sin^2(a) / l^2),
+//   dK/dsigma = 2 K / sigma,  dK/dl = K 4 sin^2(a) / l^3,
+//   dK/dp = K (2 pi d / (l^2 p^2)) sin(2a).
+// sin(a) and cos(a) come from one sincospi(d / p) (the forward needs sinpi
+// alone), d / p as d times the host's 1 / p: exact argument reduction, so a
+// pair a whole number of periods apart gives s2 when d / p is exact, and
+// sin(2a) = 2 sin cos.  Every position alike, no diagonal: d = 0 gives s2
+// exp(-0) = s2, and the sign of the difference drops out of |.| and of the
+// squares, so x1 == x2 gives a bitwise symmetric K.
+//
+// Dot product:  K_ij = sigma^2 + sum_d x1_id x2_jd in coordinate order (the
+// product commutes, so x1 == x2 is bitwise symmetric), dK/dsigma = 2 sigma:
+// the reverse is the sum of the adjoint.
+namespace {
+
+// cn = -2 / l^2
+__device__ __forceinline__ double per_k(double d, double s2, double inv_p, double cn) {
+  const double s = sinpi(d * inv_p);
+  return s2 * exp(cn * (s * s));
+}
+// as += a K, al += a K sin^2, ap += a K d sin cos
+__device__ __forceinline__ void per_acc(double a, double d, double s2, double inv_p, double cn, double& as,
+                                        double& al, double& ap) {
+  double s, c;
+  sincospi(d * inv_p, &s, &c);
+  const double ss = s * s;
+  const double ak = a * (s2 * exp(cn * ss));
+  as += ak;
+  al += ak * ss;
+  ap += ak * (d * (s * c));
+}
+
+__global__ __launch_bounds__(256) void k_gp_per_fwd_col2(const double* __restrict__ x1, int n1,
+                                                         const double* __restrict__ x2, int n2, double s2,
+                                                         double inv_p, double cn, double* __restrict__ K, int ldk) {
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          const double2 xi = xr[p];
+          double2 v;
+          v.x = per_k(fabs(xi.x - xj), s2, inv_p, cn);
+          v.y = per_k(fabs(xi.y - xj), s2, inv_p, cn);
+          col[p] = v;
+        }
+      }
+    }
+  }
+}
+
+// Generic form: any n1 and ldk (rows n1 .. ldk - 1 are not written)
+__global__ __launch_bounds__(256) void k_gp_per_fwd(const double* __restrict__ x1, int n1,
+                                                    const double* __restrict__ x2, int n2, double s2, double inv_p,
+                                                    double cn, double* __restrict__ K, int ldk) {
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double* col = K + (size_t)j * ldk;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256)
+      col[i] = per_k(fabs(x1[i] - xj), s2, inv_p, cn);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gp_per_nd_fwd(const double* __restrict__ x1, int n1,
+                                                       const double* __restrict__ x2, int n2, int D, double s2,
+                                                       double inv_p, double cn, double* __restrict__ K, int ldk) {
+  extern __shared__ double xj[];
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double* xi = x1 + (size_t)i * D;
+      double d2 = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double t = xi[d] - xj[d];
+        d2 += t * t;
+      }
+      K[i + (size_t)j * ldk] = per_k(sqrt(d2), s2, inv_p, cn);
+    }
+  }
+}
+
+// a workgroup's three sums -> part[3 b ..]
+__device__ __forceinline__ void per_store_partials(double as, double al, double ap, double* lds,
+                                                   double* __restrict__ part) {
+  const double ss = block_sum(as, lds);
+  __syncthreads();
+  const double sl = block_sum(al, lds);
+  __syncthreads();
+  const double sp = block_sum(ap, lds);
+  if (threadIdx.x == 0) {
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    part[3 * b + 0] = ss;
+    part[3 * b + 1] = sl;
+    part[3 * b + 2] = sp;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gp_per_rev_partials_col2(const double* __restrict__ x1, int n1,
+                                                                  const double* __restrict__ x2, int n2, double s2,
+                                                                  double inv_p, double cn,
+                                                                  const double* __restrict__ Ka, int lda,
+                                                                  double* __restrict__ part) {
+  __shared__ double lds[16];
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  double as = 0.0, al = 0.0, ap = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+      double2 a[4], xi[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          a[k] = col[p];
+          xi[k] = xr[p];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          per_acc(a[k].x, fabs(xi[k].x - xj), s2, inv_p, cn, as, al, ap);
+          per_acc(a[k].y, fabs(xi[k].y - xj), s2, inv_p, cn, as, al, ap);
+        }
+      }
+    }
+  }
+  per_store_partials(as, al, ap, lds, part);
+}
+
+// Generic form, D >= 1 (x2_j staged in LDS; D == 1 from the difference)
+__global__ __launch_bounds__(256) void k_gp_per_rev_partials(const double* __restrict__ x1, int n1,
+                                                             const double* __restrict__ x2, int n2, int D, double s2,
+                                                             double inv_p, double cn, const double* __restrict__ Ka,
+                                                             int lda, double* __restrict__ part) {
+  extern __shared__ double xj[];
+  __shared__ double lds[16];
+  double as = 0.0, al = 0.0, ap = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    const double* col = Ka + (size_t)j * lda;
+    const double xj0 = xj[0];
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double a = col[i];
+      if (D == 1) {
+        per_acc(a, fabs(x1[i] - xj0), s2, inv_p, cn, as, al, ap);
+      } else {
+        const double* xi = x1 + (size_t)i * D;
+        double d2 = 0.0;
+        for (int d = 0; d < D; ++d) {
+          const double t = xi[d] - xj[d];
+          d2 += t * t;
+        }
+        per_acc(a, sqrt(d2), s2, inv_p, cn, as, al, ap);
+      }
+    }
+  }
+  per_store_partials(as, al, ap, lds, part);
+}
+
+// out3 += [2 ss / sigma, 4 sl / l^3, 4 pi sp / (l^2 p^2)] (sp carries sin cos = sin(2a) / 2)
+__global__ void k_gp_per_rev_final(const double* __restrict__ part, int nparts, double sigma, double l, double p,
+                                   double* out3) {
+  __shared__ double lds[16];
+  double ss = 0.0, sl = 0.0, sp = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+    ss += part[3 * i];
+    sl += part[3 * i + 1];
+    sp += part[3 * i + 2];
+  }
+  ss = block_sum(ss, lds);
+  __syncthreads();
+  sl = block_sum(sl, lds);
+  __syncthreads();
+  sp = block_sum(sp, lds);
+  if (threadIdx.x == 0) {
+    out3[0] += ss * 2 / sigma;
+    out3[1] += 4 * sl / (l * l * l);
+    out3[2] += 4 * 3.14159265358979323846 * sp / (l * l * p * p);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gp_dot_fwd_col2(const double* __restrict__ x1, int n1,
+                                                         const double* __restrict__ x2, int n2, double s2,
+                                                         double* __restrict__ K, int ldk) {
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          const double2 xi = xr[p];
+          double2 v;
+          v.x = s2 + xi.x * xj;
+          v.y = s2 + xi.y * xj;
+          col[p] = v;
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gp_dot_fwd(const double* __restrict__ x1, int n1,
+                                                    const double* __restrict__ x2, int n2, double s2,
+                                                    double* __restrict__ K, int ldk) {
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double* col = K + (size_t)j * ldk;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) col[i] = s2 + x1[i] * xj;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gp_dot_nd_fwd(const double* __restrict__ x1, int n1,
+                                                       const double* __restrict__ x2, int n2, int D, double s2,
+                                                       double* __restrict__ K, int ldk) {
+  extern __shared__ double xj[];
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double* xi = x1 + (size_t)i * D;
+      double dot = 0.0;
+      for (int d = 0; d < D; ++d) dot += xi[d] * xj[d];
+      K[i + (size_t)j * ldk] = s2 + dot;
+    }
+  }
+}
+
+// The dot product's reverse: per-workgroup sums of the n1 x n2 adjoint over the same walks
+__global__ __launch_bounds__(256) void k_gp_dot_rev_partials_col2(int n1, int n2, const double* __restrict__ Ka,
+                                                                  int lda, double* __restrict__ part) {
+  __shared__ double lds[16];
+  const int np = n1 >> 1;
+  double as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+      double2 a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        a[k] = p < np ? col[p] : make_double2(0.0, 0.0);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) as += a[k].x + a[k].y;
+    }
+  }
+  const double s = block_sum(as, lds);
+  if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void k_gp_dot_rev_partials(int n1, int n2, const double* __restrict__ Ka, int lda,
+                                                             double* __restrict__ part) {
+  __shared__ double lds[16];
+  double as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double* col = Ka + (size_t)j * lda;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) as += col[i];
+  }
+  const double s = block_sum(as, lds);
+  if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ void k_gp_dot_rev_final(const double* __restrict__ part, int nparts, double sigma, double* out1) {
+  __shared__ double lds[16];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += part[i];
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) out1[0] += 2 * sigma * s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smg_gp_periodic_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double l, double p, double* K, int ldk) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma, inv_p = 1.0 / p, cn = -2.0 / (l * l);
+  if (D > 1)
+    hipLaunchKernelGGL(k_gp_per_nd_fwd, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2,
+                       n2, D, s2, inv_p, cn, K, ldk);
+  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
+    hipLaunchKernelGGL(k_gp_per_fwd_col2, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2,
+                       inv_p, cn, K, ldk);
+  else
+    hipLaunchKernelGGL(k_gp_per_fwd, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, inv_p, cn,
+                       K, ldk);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+int smg_gp_periodic_cov_rev(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double l, double p, const double* Kadj, int ldka, double* out3) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!x1 || !x2 || !Kadj || !out3 || ldka < n1) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma, inv_p = 1.0 / p, cn = -2.0 / (l * l);
+  const bool col2 = D == 1 && col2_ok(x1, 2, n1) && col2_ok(Kadj, ldka, n1);
+  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
+  const int nb = (int)(grid.x * grid.y);
+  double* part = smg_ws(ctx, SMG_WS_RED, 3 * (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  if (col2)
+    hipLaunchKernelGGL(k_gp_per_rev_partials_col2, grid, dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, inv_p, cn, Kadj,
+                       ldka, part);
+  else
+    hipLaunchKernelGGL(k_gp_per_rev_partials, grid, dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2, n2, D, s2,
+                       inv_p, cn, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_per_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, p, out3);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+int smg_gp_dot_prod_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
+                            double* K, int ldk) {
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const double s2 = sigma * sigma;
+  if (D > 1)
+    hipLaunchKernelGGL(k_gp_dot_nd_fwd, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2,
+                       n2, D, s2, K, ldk);
+  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
+    hipLaunchKernelGGL(k_gp_dot_fwd_col2, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, K,
+                       ldk);
+  else
+    hipLaunchKernelGGL(k_gp_dot_fwd, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, K, ldk);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+int smg_gp_dot_prod_cov_rev(smg_ctx* ctx, int n1, int n2, double sigma, const double* Kadj, int ldka, double* out1) {
+  if (!ctx || n1 < 0 || n2 < 0) return SMG_ERR_ARG;
+  if (n1 == 0 || n2 == 0) return SMG_OK;
+  if (!Kadj || !out1 || ldka < n1) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const bool col2 = col2_ok(Kadj, ldka, n1);
+  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
+  const int nb = (int)(grid.x * grid.y);
+  double* part = smg_ws(ctx, SMG_WS_RED, (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  if (col2)
+    hipLaunchKernelGGL(k_gp_dot_rev_partials_col2, grid, dim3(256), 0, ctx->stream, n1, n2, Kadj, ldka, part);
+  else
+    hipLaunchKernelGGL(k_gp_dot_rev_partials, grid, dim3(256), 0, ctx->stream, n1, n2, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_dot_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, out1);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+}  // extern "C"

@@ -132,6 +132,12 @@ _SIGS = {
     "smg_gp_cross_cov_fwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _D, _P, _I]),
     "smg_gp_cross_cov_rev": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _D, _P, _I, _P]),
     "smg_gp_ard_cross_cov_rev": (_I, [_P, _I, _P, _I, _P, _I, _I, _D, _P, _P, _I, _P]),
+    # gp_periodic_cov / gp_dot_prod_cov, square (x1 == x2) and cross:
+    # (ctx, x1, n1, x2, n2, D, sigma, l, p, ...) and (ctx, x1, n1, x2, n2, D, sigma, K, ldk) / (ctx, n1, n2, sigma, ...)
+    "smg_gp_periodic_cov_fwd": (_I, [_P, _P, _I, _P, _I, _I, _D, _D, _D, _P, _I]),
+    "smg_gp_periodic_cov_rev": (_I, [_P, _P, _I, _P, _I, _I, _D, _D, _D, _P, _I, _P]),
+    "smg_gp_dot_prod_cov_fwd": (_I, [_P, _P, _I, _P, _I, _I, _D, _P, _I]),
+    "smg_gp_dot_prod_cov_rev": (_I, [_P, _I, _I, _D, _P, _I, _P]),
     "smg_log_sum_exp_fwd": (_I, [_P, _P, _L, _P]),
     "smg_log_sum_exp_rev": (_I, [_P, _P, _L, _D, _D, _P]),
     "smg_lgamma_fwd": (_I, [_P, _P, _L, _P]),

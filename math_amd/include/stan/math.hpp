@@ -16,6 +16,7 @@
 #include <stan/math/rev/fun/gp_matern_cov.hpp>
 #include <stan/math/rev/fun/gp_ard_cov.hpp>
 #include <stan/math/rev/fun/gp_cross_cov.hpp>
+#include <stan/math/rev/fun/gp_periodic_cov.hpp>
 #include <stan/math/rev/fun/cholesky_decompose.hpp>
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/multiply.hpp>

@@ -40,6 +40,7 @@
 #include <stan/math/rev/fun/gp_matern_cov.hpp>
 #include <stan/math/rev/fun/gp_ard_cov.hpp>
 #include <stan/math/rev/fun/gp_cross_cov.hpp>
+#include <stan/math/rev/fun/gp_periodic_cov.hpp>
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
@@ -1081,6 +1082,65 @@ STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_matern32_cov, SMG_GP_MATERN32)
 STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS(gp_matern52_cov, SMG_GP_MATERN52)
 
 #undef STAN_MATH_AMD_GP_CROSS_POINT_OVERLOADS
+
+// ---- gp_periodic_cov and gp_dot_prod_cov over D-dimensional points
+// (rev/fun/gp_periodic_cov.hpp: the checks' order and wording, the degenerate
+// shapes; the cross overloads' packing and point-size check)
+namespace internal {
+template <typename T_x>
+inline void gp_dot_prod_check_points(const char* fn, const char* name, const std::vector<T_x>& x) {
+  for (size_t i = 0; i < x.size(); ++i)
+    for (int d = 0; d < int(x[i].size()); ++d) gp_dot_prod_check_entry(fn, name, x[i](d));
+}
+}  // namespace internal
+
+template <int R, int C, typename A, typename T_s, typename T_l, typename T_p,
+          typename = internal::gp_periodic_kinds<T_s, T_l, T_p>>
+inline dev_var_matrix gp_periodic_cov(const std::vector<Eigen::Matrix<double, R, C>, A>& x, const T_s& sigma,
+                                      const T_l& l, const T_p& p) {
+  const char* fn = "gp_periodic_cov";
+  const internal::gp_periodic_hyper h = internal::gp_periodic_hyper_of(sigma, l, p);
+  h.check(fn);
+  internal::gp_cross_check_points_not_nan(fn, "element of x", x, false);
+  const int D = internal::gp_cross_points_dim(x, x);
+  const dev_data<double> xd = internal::gp_cross_pack_points(x, D);
+  return internal::gp_periodic_cov_dev(fn, xd, xd, D > 0 ? D : 1, h, dev_structure::symmetric);
+}
+template <int R, int C, typename A, typename T_s, typename T_l, typename T_p,
+          typename = internal::gp_periodic_kinds<T_s, T_l, T_p>>
+inline dev_var_matrix gp_periodic_cov(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,
+                                      const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const T_s& sigma,
+                                      const T_l& l, const T_p& p) {
+  const char* fn = "gp_periodic_cov";
+  const internal::gp_periodic_hyper h = internal::gp_periodic_hyper_of(sigma, l, p);
+  h.check(fn);
+  internal::gp_cross_check_points_not_nan(fn, "element of x1", x1, false);
+  internal::gp_cross_check_points_not_nan(fn, "element of x2", x2, false);
+  const int D = internal::gp_cross_points_dim(x1, x2);
+  return internal::gp_periodic_cov_dev(fn, internal::gp_cross_pack_points(x1, D), internal::gp_cross_pack_points(x2, D),
+                                       D > 0 ? D : 1, h, dev_structure::general);
+}
+
+template <int R, int C, typename A>
+inline dev_var_matrix gp_dot_prod_cov(const std::vector<Eigen::Matrix<double, R, C>, A>& x, const var& sigma) {
+  const char* fn = "gp_dot_prod_cov";
+  internal::gp_dot_prod_check_sigma(fn, sigma.val());
+  internal::gp_dot_prod_check_points(fn, "x", x);
+  const int D = internal::gp_cross_points_dim(x, x);
+  const dev_data<double> xd = internal::gp_cross_pack_points(x, D);
+  return internal::gp_dot_prod_cov_dev(fn, xd, xd, D > 0 ? D : 1, sigma.val(), sigma.vi_, dev_structure::symmetric);
+}
+template <int R, int C, typename A>
+inline dev_var_matrix gp_dot_prod_cov(const std::vector<Eigen::Matrix<double, R, C>, A>& x1,
+                                      const std::vector<Eigen::Matrix<double, R, C>, A>& x2, const var& sigma) {
+  const char* fn = "gp_dot_prod_cov";
+  internal::gp_dot_prod_check_sigma(fn, sigma.val());
+  internal::gp_dot_prod_check_points(fn, "x1", x1);
+  internal::gp_dot_prod_check_points(fn, "x2", x2);
+  const int D = internal::gp_cross_points_dim(x1, x2);
+  return internal::gp_dot_prod_cov_dev(fn, internal::gp_cross_pack_points(x1, D), internal::gp_cross_pack_points(x2, D),
+                                       D > 0 ? D : 1, sigma.val(), sigma.vi_, dev_structure::general);
+}
 
 }  // namespace math
 }  // namespace stan
