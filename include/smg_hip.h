@@ -870,6 +870,24 @@ int smg_poisson_log_glm(smg_ctx* ctx, const int* y, const double* x,
                         long long R, int M, long long ldx,
                         const double* alpha_beta, double* ws, double* out);
 
+/* neg_binomial_2_log_glm_lpmf(y | x, alpha, beta, phi), scalar alpha and
+ * precision phi (Stan Math 3.0.0), ONE fused pass over x:
+ *   alpha_beta_phi = [alpha, beta(M), phi] (device);
+ *   out (M + 6 doubles) = [A, sum theta', x^T theta' (M), B, C, D, phi'] with
+ *   theta = x beta + alpha, lse = log(exp theta + phi), s = exp theta / (exp theta + phi),
+ *   A = sum (y + phi) lse, B = sum y theta, C = sum lgamma(y + 1), D = sum lgamma(y + phi),
+ *   theta' = y - (y + phi) s,
+ *   phi' = sum (1 - (y + phi)(1 - s)/phi) + (log phi - lse) + (digamma(y + phi) - digamma(phi));
+ *   logp = -C + R (phi log phi - lgamma phi) - A + B + D is composed by the caller.
+ * lse, s and 1 - s are evaluated from exp(-|theta - log phi|), so every output
+ * is finite for finite theta of any size (the reference is NaN beyond theta = 709).
+ * M <= 256.  ws: >= smg_neg_binomial_2_log_glm_ws_doubles(R, M).  R == 0
+ * writes zeros.  y >= 0 and phi > 0 are checked by the caller. */
+long long smg_neg_binomial_2_log_glm_ws_doubles(long long R, int M);
+int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x,
+                               long long R, int M, long long ldx,
+                               const double* alpha_beta_phi, double* ws, double* out);
+
 /* categorical_logit_glm_lpmf<false>(y | x, alpha, beta)
  * (prim/mat/prob/categorical_logit_glm_lpmf.hpp:38-146): x R x M
  * (column-major, ld ldx), alpha_beta = [alpha(C), beta(M x C column-major)],

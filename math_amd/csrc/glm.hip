@@ -2,6 +2,7 @@
 //   KIND 0  bernoulli_logit_glm_lpmf  (y int in {0,1})
 //   KIND 1  normal_id_glm_lpdf        (y double, scalar sigma)
 //   KIND 2  poisson_log_glm_lpmf      (y int >= 0)
+//   KIND 3  neg_binomial_2_log_glm_lpmf (y int >= 0, scalar precision phi)
 // They differ only in the per-row function of the linear predictor; the
 // x-streaming, the x^T theta' product and the deterministic reductions are
 // shared.
@@ -15,6 +16,19 @@
 //   theta = x beta + alpha;  theta' = y - exp(theta)
 //   logp = -sum lgamma(y + 1) + sum(y theta - exp(theta))
 //   (device: out = [sum(y theta - exp theta), sum theta', x^T theta', sum lgamma(y + 1)])
+// KIND 3: neg_binomial_2_log_glm_lpmf of Stan Math 3.0.0, restated so that no
+// term forms exp(theta): with d = theta - log phi and e = exp(-|d|) in (0, 1],
+//   lse = log(exp theta + phi) = max(theta, log phi) + log1p(e)
+//   s = exp theta / (exp theta + phi) = d >= 0 ? 1 / (1 + e) : e / (1 + e)
+//   1 - s = the same with the sign of d flipped
+//   theta' = y - (y + phi) s
+//   phi'   = sum (1 - (y + phi)(1 - s) / phi) + (log phi - lse)
+//                + (digamma(y + phi) - digamma(phi))
+//   logp = -C + N (phi log phi - lgamma phi) - A + B + D  (composed by the host)
+//   (device: out = [A = sum (y + phi) lse, sum theta', x^T theta', B = sum y theta,
+//                   C = sum lgamma(y + 1), D = sum lgamma(y + phi), phi'])
+// Every sum is finite for finite theta of any size (the reference's own
+// exp(theta) / (exp(theta) + phi) is inf / inf beyond theta = 709).
 //
 // KIND 0:
 // Reference: prim/mat/prob/bernoulli_logit_glm_lpmf.hpp:46-138
@@ -48,6 +62,7 @@
 #include <cstdlib>
 
 #include "smg_internal.h"
+#include "special_dev.h"  // dev_lgamma, dev_digamma (KIND 3)
 
 namespace {
 
@@ -84,11 +99,18 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   for (int c = t; c < MMAX; c += NT) beta[c] = c < M ? ab[1 + c] : 0.0;
   const double alpha = ab[0];
   const double inv_sigma = KIND == 1 ? 1.0 / ab[1 + M] : 0.0;
+  const double phi = KIND == 3 ? ab[1 + M] : 0.0;
+  const double log_phi = KIND == 3 ? log(phi) : 0.0;
+  // KIND 3 without columns (M == 0, x may be null): every x load reads the zero page
+  const bool nox = KIND == 3 && M == 0;
+  const double* __restrict__ xb = nox ? g_glm_zero : x;
+  const long long ldc = nox ? 0 : ldx, rend = nox ? 1 : R;
   const long long ntiles = (R + RB - 1) / RB;
   double gacc[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) gacc[q] = 0.0;
   double lp_acc = 0.0, ga_acc = 0.0, c_acc = 0.0;
+  double b_acc = 0.0, d_acc = 0.0, f_acc = 0.0;  // KIND 3: B, D and phi'
   double xc[Q], xn[Q];
   double yc = 0.0, yn = 0.0;  // the row's y (as double), loaded one tile ahead with x
   // Loads are straight-line code: addresses are clamped into x and the
@@ -97,13 +119,14 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   // that waiting for it leaves the x loads in flight (vmcnt counts in order).
   auto load = [&](double (&v)[Q], double& yv_, long long tile) {
     const long long gr = tile * RB + r;
-    const size_t rc = (size_t)(gr < R ? gr : R - 1);
-    yv_ = KIND == 1 ? yd[rc] : (double)y[rc];
+    const size_t ry = (size_t)(gr < R ? gr : R - 1);
+    const size_t rc = (size_t)(gr < rend ? gr : rend - 1);
+    yv_ = KIND == 1 ? yd[ry] : (double)y[ry];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const int c = g + G * q;
       const int cc = c < M ? c : M - 1;
-      const double* px = x + rc + (size_t)cc * ldx;
+      const double* px = xb + rc + (size_t)cc * ldc;
       v[q] = NTL ? __builtin_nontemporal_load(px) : *px;
     }
   };
@@ -135,12 +158,28 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
         const double ys = (cy - eta - alpha) * inv_sigma;
         lp = ys * ys;
         th = ys * inv_sigma;
-      } else {
+      } else if (KIND == 2) {
         const double yi = cy;
         const double theta = eta + alpha;
         const double ex = exp(theta);
         lp = yi * theta - ex;
         th = yi - ex;
+      } else {
+        const double yi = cy;
+        const double theta = eta + alpha;
+        const double d = theta - log_phi;
+        const double e = exp(-fabs(d));  // in [0, 1]: never exp(theta) itself
+        const double lse = fmax(theta, log_phi) + log1p(e);
+        const double inv = 1.0 / (1.0 + e);
+        const double s = d >= 0.0 ? inv : e * inv;
+        const double s1 = d >= 0.0 ? e * inv : inv;  // 1 - s
+        const double yp = yi + phi;
+        lp = yp * lse;
+        th = yi - yp * s;
+        if (g == 0) {
+          b_acc += yi * theta;
+          f_acc += (1.0 - yp * s1 / phi) + (log_phi - lse);
+        }
       }
       if (g == 0) {  // one thread per row accumulates the row's terms
         lp_acc += lp;
@@ -175,12 +214,26 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
       const long long gr = tl2 * RB + r;
       if (gr < R) c_acc += lgamma((double)y[gr] + 1.0);
     }
+  if (KIND == 3) {  // the terms of y and phi alone, off the streaming loop, over all threads
+    const double dg_phi = dev_digamma(phi);
+    for (long long k = t / RB;; k += NT / RB) {
+      const long long tl2 = blockIdx.x + k * gridDim.x;
+      if (tl2 >= ntiles) break;
+      const long long gr = tl2 * RB + r;
+      if (gr < R) {
+        const double yi = (double)y[gr];
+        c_acc += dev_lgamma(yi + 1.0);
+        d_acc += dev_lgamma(yi + phi);
+        f_acc += dev_digamma(yi + phi) - dg_phi;
+      }
+    }
+  }
   // column sums over the RB rows of each column group: RB adjacent lanes
 #pragma unroll
   for (int q = 0; q < Q; ++q)
     for (int off = RB / 2; off > 0; off >>= 1) gacc[q] += __shfl_xor(gacc[q], off, RB);
   const bool extra = KIND == 2 || (KIND == 0 && check_y);
-  const int W = M + 2 + (extra ? 1 : 0);
+  const int W = KIND == 3 ? M + 6 : M + 2 + (extra ? 1 : 0);
   double* p = part + (size_t)blockIdx.x * W;
   __syncthreads();
   const double lp = block_sum(lp_acc, lds);
@@ -195,6 +248,22 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
     p[0] = lp;
     p[1] = ga;
     if (extra) p[M + 2] = cs;
+  }
+  if (KIND == 3) {  // [.., B, C, D, phi'] behind beta'
+    __syncthreads();
+    const double bs = block_sum(b_acc, lds);
+    __syncthreads();
+    const double c3 = block_sum(c_acc, lds);
+    __syncthreads();
+    const double ds = block_sum(d_acc, lds);
+    __syncthreads();
+    const double fs = block_sum(f_acc, lds);
+    if (t == 0) {
+      p[M + 2] = bs;
+      p[M + 3] = c3;
+      p[M + 4] = ds;
+      p[M + 5] = fs;
+    }
   }
   if (r == 0)
 #pragma unroll
@@ -593,6 +662,22 @@ int smg_poisson_log_glm(smg_ctx* ctx, const int* y, const double* x, long long R
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<2>(ctx->stream, y, x, R, M, ldx, ab, ws);
   smg_reduce_partials(ctx, ws, nb, M + 3, out, 0);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// neg_binomial_2_log_glm_lpmf: the fused pass (M <= 256), partial width M + 6
+long long smg_neg_binomial_2_log_glm_ws_doubles(long long R, int M) {
+  return (long long)glm_blocks(R) * ((M > 0 ? M : 0) + 6);
+}
+
+int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
+                               long long ldx, const double* abp, double* ws, double* out) {
+  if (!ctx || R < 0 || M < 0 || M > MMAX || !abp || !ws || !out) return SMG_ERR_ARG;
+  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  smg_prof_scope prof(ctx, SMG_FAM_GLM);
+  const int nb = glm_launch<3>(ctx->stream, y, x, R, M, ldx, abp, ws);
+  smg_reduce_partials(ctx, ws, nb, M + 6, out, 0);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
 }

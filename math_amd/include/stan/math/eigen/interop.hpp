@@ -44,6 +44,7 @@
 #include <stan/math/rev/fun/multi_normal_cholesky_lpdf.hpp>
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/neg_binomial_2_log_glm_lpmf.hpp>
 #include <stan/math/rev/fun/spd_functors.hpp>
 #include <stan/math/rev/fun/lgamma.hpp>
 #include <stan/math/rev/fun/log_sum_exp.hpp>
@@ -537,6 +538,19 @@ inline double bernoulli_logit_glm_lpmf(const std::vector<int>& y, const matrix_d
         "bernoulli_logit_glm_lpmf: Vector of dependent variables has dimension = " +
         std::to_string(y.size()) + ", expecting dimension = " + std::to_string(x.rows()));
   return bernoulli_logit_glm_lpmf<propto>(y, xv, int(x.cols()), alpha, b);
+}
+
+/** neg_binomial_2_log_glm_lpmf(y, x, alpha, beta, phi) with Eigen x / beta;
+ * alpha, beta and phi each var or double (all double: a double). */
+template <bool propto = false, typename T_alpha, typename T_b, int RB, typename T_precision>
+inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const matrix_d& x, const T_alpha& alpha,
+                                        const Eigen::Matrix<T_b, RB, 1>& beta, const T_precision& phi) {
+  std::vector<T_b> b(beta.data(), beta.data() + beta.size());
+  std::vector<double> xv(x.data(), x.data() + x.size());
+  if (y.size() != size_t(x.rows()))
+    internal::glm_size_mismatch("neg_binomial_2_log_glm_lpmf", "Vector of dependent variables",
+                                (long long)y.size(), x.rows());
+  return neg_binomial_2_log_glm_lpmf<propto>(y, xv, int(x.cols()), alpha, b, phi);
 }
 
 namespace internal {

@@ -33,8 +33,10 @@ namespace internal {
 
 // index (global: row0 = the shard's first row) and value of the first
 // negative y (host copy: error path only); a rank whose own rows are all
-// non-negative (the flag came from another rank) names no element
-inline void glm_throw_negative_y(const char* fn, const int* y, long long n, long long row0 = 0) {
+// non-negative (the flag came from another rank) names no element.  `name`:
+// the reference's name of y in the message (poisson's by default).
+inline void glm_throw_negative_y(const char* fn, const int* y, long long n, long long row0 = 0,
+                                 const char* name = "Vector of dependent variables") {
   smg_ctx* c = amd::ctx();
   const long long chunk = 1 << 20;
   std::vector<int> h(size_t(n > chunk ? chunk : (n > 0 ? n : 0)));
@@ -48,13 +50,12 @@ inline void glm_throw_negative_y(const char* fn, const int* y, long long n, long
     for (long long i = 0; i < k; ++i)
       if (h[size_t(i)] < 0) {
         std::ostringstream m;
-        m << fn << ": Vector of dependent variables[" << row0 + i0 + i + 1 << "] is " << h[size_t(i)]
-          << ", but must be >= 0!";
+        m << fn << ": " << name << "[" << row0 + i0 + i + 1 << "] is " << h[size_t(i)] << ", but must be >= 0!";
         throw std::domain_error(m.str());
       }
   }
-  throw std::domain_error(std::string(fn) +
-                          ": Vector of dependent variables is negative (on another rank's rows), but must be >= 0!");
+  throw std::domain_error(std::string(fn) + ": " + name +
+                          " is negative (on another rank's rows), but must be >= 0!");
 }
 
 template <bool propto>
