@@ -171,6 +171,10 @@ int smg_profile_enable(smg_ctx* ctx, int on);
 int smg_profile_read(smg_ctx* ctx, int family, double* total_ms_host, long long* count_host);
 /* algorithmic flops issued per family since enable (GEMM: 2mnk per call) */
 int smg_profile_flops(smg_ctx* ctx, int family, double* flops_host);
+/* bytes this context has zeroed on the device (smg_memset with value 0, the
+ * queued smg_memset_async zeroings once issued) since creation or the last
+ * smg_profile_enable: what the tape's adjoint clears cost an evaluation */
+unsigned long long smg_zeroed_bytes(const smg_ctx* ctx);
 
 /* deterministic synthetic data on the device (SplitMix64, oracle/gen.h):
  * out[i] = a + (b - a) * u_i  /  out[i] = (u_i < p) */

@@ -577,6 +577,7 @@ int smg_zero_ranges_impl(smg_ctx* ctx, hipStream_t stream, const std::pair<void*
   for (int i = 0; i < count; ++i) {
     const size_t b = r[i].second;
     if (!b) continue;
+    ctx->zeroed_bytes += b;
     if ((reinterpret_cast<uintptr_t>(r[i].first) & 7) || (b & 7)) {  // (not a range of doubles)
       SMG_HIP_TRY(hipMemsetAsync(r[i].first, 0, b, stream));
       continue;
@@ -793,8 +794,11 @@ int smg_profile_enable(smg_ctx* ctx, int on) {
     ctx->prof_count[i] = 0;
     ctx->prof_flops[i] = 0;
   }
+  ctx->zeroed_bytes = 0;
   return SMG_OK;
 }
+
+unsigned long long smg_zeroed_bytes(const smg_ctx* ctx) { return ctx ? ctx->zeroed_bytes : 0; }
 
 int smg_profile_read(smg_ctx* ctx, int family, double* ms, long long* count) {
   if (family < 0 || family >= SMG_FAM_COUNT) return SMG_ERR_ARG;

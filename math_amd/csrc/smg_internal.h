@@ -121,6 +121,9 @@ struct smg_ctx {
   double prof_ms[SMG_FAM_COUNT];
   double prof_flops[SMG_FAM_COUNT];
   long long prof_count[SMG_FAM_COUNT];
+  // bytes zeroed through k_zero_ranges / hipMemsetAsync(0) on any stream
+  // (smg_zeroed_bytes; reset with the counters above)
+  unsigned long long zeroed_bytes;
   // RCCL communicator (opaque)
   void* comm;
 };

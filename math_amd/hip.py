@@ -61,6 +61,7 @@ _SIGS = {
     "smg_profile_enable": (_I, [_P, _I]),
     "smg_profile_read": (_I, [_P, _I, ctypes.POINTER(_D), ctypes.POINTER(_L)]),
     "smg_profile_flops": (_I, [_P, _I, ctypes.POINTER(_D)]),
+    "smg_zeroed_bytes": (ctypes.c_ulonglong, [_P]),
     "smg_fill_unif": (_I, [_P, _P, _L, ctypes.c_ulonglong, _D, _D, _D]),
     "smg_fill_bernoulli": (_I, [_P, _P, _L, ctypes.c_ulonglong, _D]),
     "smg_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _D, _P, _I, _P, _I, _D, _P, _I]),

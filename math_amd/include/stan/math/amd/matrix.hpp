@@ -108,6 +108,12 @@ class structured_adjoint_sink {
    * that it holds what the reference's varis would (the closed form never
    * formed it). */
   virtual void expand_adjoint() {}
+  /** By a consumer that knows at its construction that it will write the
+   * node's output adjoint densely (a factorisation whose reverse cannot take
+   * the closed form): a node that then adds into its own operand's dense
+   * adjoint queues that buffer's zeroing now (dev_matrix_vari::want_adjoint)
+   * and passes the notice on. */
+  virtual void expect_dense_adjoint() {}
   /** The factor's explicit inverse W = L^{-1} (device, n x n, ld n, lower;
    * stored zeros above the diagonal inside its diagonal 64 x 64 tiles) when
    * the factorisation formed it anyway, with the context's stream already
@@ -160,11 +166,12 @@ inline size_t& materialisation_count() {
 class dev_matrix_vari {
   double* val_;  // device, column-major, ld = rows_ (allocated at construction; see val())
   deferred_value_source* pending_ = nullptr;  // the producer still to form the values
+  double* adj_;      // device, column-major, registered with the tape (see adj())
+  size_t adj_slot_;  // its entry in the tape's dev_adj_stack_
 
  public:
   const int rows_;
   const int cols_;
-  double* adj_;  // device, column-major, registered with the tape
   dev_structure structure_;
   double* aux_;  // node-specific device side data (e.g. Cholesky diagonal-block inverses)
   // set on transpose(A)'s output: multiply(A, transpose(A)) recognises the
@@ -175,15 +182,29 @@ class dev_matrix_vari {
 
   dev_matrix_vari(int rows, int cols, dev_structure s = dev_structure::general)
       : val_(amd::alloc_doubles(size_t(rows) * cols)),
+        adj_(amd::alloc_doubles(size_t(rows) * cols)),
+        adj_slot_(register_device_adjoint(adj_, size_t(rows) * cols)),
         rows_(rows),
         cols_(cols),
-        adj_(amd::alloc_doubles(size_t(rows) * cols)),
         structure_(s),
-        aux_(nullptr) {
-    register_device_adjoint(adj_, size_t(rows) * cols);
-  }
+        aux_(nullptr) {}
 
   size_t size() const { return size_t(rows_) * cols_; }
+
+  /** The adjoints, for every node that adds into them or reads them densely.
+   * A large buffer starts unzeroed (grad.hpp register_device_adjoint): its
+   * first such user zeroes it here, so a buffer no node ever touches -- K's,
+   * K + dI's and L's under the closed-form reverse, which passes an
+   * inverse_adjoint from sink to sink instead -- is never cleared at all.  The
+   * pointer itself never changes. */
+  double* adj() {
+    clear_device_adjoint(adj_slot_, true);
+    return adj_;
+  }
+  /** By the constructor of a node whose chain() will add into the adjoints
+   * (or read them) unconditionally: the zeroing is queued now, on the zeroing
+   * stream beside the rest of the forward pass, not in the reverse sweep. */
+  void want_adjoint() { clear_device_adjoint(adj_slot_, false); }
 
   /** The values, for every reader: a deferred matrix's are formed first, by
    * the kernels its producer's constructor would have launched (the same
@@ -223,7 +244,7 @@ class dev_var_matrix {
   int cols() const { return vi_->cols_; }
   size_t size() const { return vi_->size(); }
   const double* val_ptr() const { return vi_->val(); }
-  double* adj_ptr() const { return vi_->adj_; }
+  double* adj_ptr() const { return vi_->adj(); }
 
   /** Column-major host copy of the values (synchronising). */
   std::vector<double> val() const {
@@ -234,9 +255,10 @@ class dev_var_matrix {
   /** Column-major host copy of the adjoints (synchronising). */
   std::vector<double> adj() const {
     if (vi_->sink_) vi_->sink_->expand_adjoint();
+    const double* a = vi_->adj();
     join_device_adjoints();
     std::vector<double> h(size());
-    amd::to_host(h.data(), vi_->adj_, size());
+    amd::to_host(h.data(), a, size());
     return h;
   }
 
@@ -283,10 +305,20 @@ struct dev_operand {
   const double* data = nullptr;
   int rows = 0, cols = 0;
   const double* val() const { return vi ? vi->val() : data; }
-  double* adj() const { return vi ? vi->adj_ : nullptr; }
+  double* adj() const { return vi ? vi->adj() : nullptr; }
   size_t size() const { return size_t(rows) * size_t(cols); }
 };
-inline dev_operand operand(const dev_var_matrix& m) { return dev_operand{m.vi_, nullptr, m.rows(), m.cols()}; }
+/** m as the operand of a node whose chain() adds into m's adjoint densely:
+ * its zeroing is queued here, at the consumer's construction. */
+inline dev_operand operand(const dev_var_matrix& m) {
+  m.vi_->want_adjoint();
+  return dev_operand{m.vi_, nullptr, m.rows(), m.cols()};
+}
+/** m as the operand of a node that may pass m's adjoint on in structured form
+ * (add_diag): nothing is queued; a dense write zeroes it then (adj()). */
+inline dev_operand structured_operand(const dev_var_matrix& m) {
+  return dev_operand{m.vi_, nullptr, m.rows(), m.cols()};
+}
 inline dev_operand operand(const dev_data<double>& d) { return dev_operand{nullptr, d.data(), d.rows(), d.cols()}; }
 }  // namespace internal
 
@@ -490,9 +522,9 @@ class dev_to_host_vari : public vari {
     amd::check(smg_memcpy_h2d(c, dst, stage, b.n * sizeof(double)), "to_host");
     const int mode = block_pack_mode(b.layout);
     if (mode < 0)
-      amd::check(smg_axpy(c, (long long)b.n, 1.0, dst, 1, node->adj_, 1), "to_host");
+      amd::check(smg_axpy(c, (long long)b.n, 1.0, dst, 1, node->adj(), 1), "to_host");
     else
-      amd::check(smg_unpack_tril_add(c, mode, mode == 2 ? int(b.n) : b.rows, dst, node->adj_, b.rows), "to_host");
+      amd::check(smg_unpack_tril_add(c, mode, mode == 2 ? int(b.n) : b.rows, dst, node->adj(), b.rows), "to_host");
     amd::check(smg_sync(c), "to_host");  // the staging buffer is reused by the next host copy
   }
 };
@@ -509,7 +541,6 @@ inline void publish_block_adjoints(size_t from) {
   auto* st = ChainableStack::instance_;
   if (from >= st->host_blocks_.size() || !amd::has_ctx()) return;
   smg_ctx* c = amd::ctx();
-  join_device_adjoints();
   const size_t nb = st->host_blocks_.size();
   std::vector<size_t> off(nb + 1, 0);  // each block's doubles in the staging area (+1: a lower block's upper sum)
   for (size_t k = from; k < nb; ++k) {
@@ -524,13 +555,14 @@ inline void publish_block_adjoints(size_t from) {
     if (!b.n) continue;
     auto* node = static_cast<dev_matrix_vari*>(b.node);
     if (node->sink_) node->sink_->expand_adjoint();
-    const double* src = node->adj_;
+    const double* src = node->adj();
+    join_device_adjoints();  // (a buffer no node touched is zeroed only now)
     const int mode = block_pack_mode(b.layout);
     const size_t cnt = off[k + 1] - off[k];
     if (mode >= 0) {
       double* t = amd::alloc_doubles(cnt);
-      amd::check(smg_pack_tril(c, mode, mode == 2 ? int(b.n) : b.rows, node->adj_, b.rows, t), "grad");
-      if (b.layout == layout_lower) amd::check(smg_sum_strict_upper(c, b.rows, node->adj_, b.rows, t + b.n), "grad");
+      amd::check(smg_pack_tril(c, mode, mode == 2 ? int(b.n) : b.rows, src, b.rows, t), "grad");
+      if (b.layout == layout_lower) amd::check(smg_sum_strict_upper(c, b.rows, src, b.rows, t + b.n), "grad");
       src = t;
     }
     amd::check(smg_memcpy_d2h(c, stage + off[k], src, cnt * sizeof(double)), "grad");
@@ -679,7 +711,7 @@ class host_to_dev_vari : public host_local_vari {
     amd::check(smg_status_armed(c, &armed), "to_dev");
     double* h = static_cast<double*>(smg_host_scratch(c, (n + 1) * sizeof(double)));
     if (!h) throw std::bad_alloc();
-    amd::check(smg_memcpy_d2h(c, h, dst_->adj_, n * sizeof(double)), "to_dev");
+    amd::check(smg_memcpy_d2h(c, h, dst_->adj(), n * sizeof(double)), "to_dev");
     if (armed) amd::check(smg_status_enqueue(c, reinterpret_cast<int*>(h + n)), "to_dev");
     amd::check(smg_sync(c), "to_dev");
     if (armed) amd::throw_if_sync(*reinterpret_cast<int*>(h + n), "to_dev", "a persistent solve");

@@ -164,9 +164,11 @@ inline eig_in prepare(const Eigen::Matrix<double, R, C, O, MR, MC>& m, const cha
       if (std::isnan(e.dd[i])) throw_not_nan(nan_fn, nan_name, i);
   return e;
 }
-/** The device operand of a prepared input (this may push the bridge vari). */
-inline dev_operand commit(const eig_in& e) {
-  if (e.node) return operand(dev_var_matrix(e.node));
+/** The device operand of a prepared input (this may push the bridge vari).
+ * structured: for a consumer that may pass a recognised node's adjoint on in
+ * structured form (matrix.hpp structured_operand). */
+inline dev_operand commit(const eig_in& e, bool structured = false) {
+  if (e.node) return structured ? structured_operand(dev_var_matrix(e.node)) : operand(dev_var_matrix(e.node));
   if (e.vd) return operand(to_dev_vars(e.vd, e.n, e.rows, e.cols));
   return operand(to_dev_data(e.dd, e.n, e.rows, e.cols));
 }
@@ -348,7 +350,7 @@ template <typename T_m, typename T_a,
                                       internal::any_var<T_m, T_a>::value>>
 inline matrix_v add_diag(const Eigen::Matrix<T_m, Eigen::Dynamic, Eigen::Dynamic>& mat, const T_a& to_add) {
   const internal::eig_in em = internal::prepare(mat);
-  const internal::dev_operand a = internal::commit(em);
+  const internal::dev_operand a = internal::commit(em, true);
   if constexpr (internal::is_var<T_a>::value)
     return internal::add_diag_output(mat, em, internal::add_diag_dev(a, to_add.val(), to_add.vi_, {}));
   else
@@ -369,7 +371,7 @@ inline matrix_v add_diag(const Eigen::Matrix<T_m, Eigen::Dynamic, Eigen::Dynamic
   }
   const internal::eig_in em = internal::prepare(mat);
   const internal::eig_in ed = internal::prepare(to_add);
-  const internal::dev_operand a = internal::commit(em);
+  const internal::dev_operand a = internal::commit(em, true);
   internal::dev_operand d = internal::commit(ed);
   d.rows = int(d.size());
   d.cols = 1;
@@ -687,7 +689,7 @@ inline mvt_dev<var> mvt_to_dev(const std::vector<const var*>& p, int n) {
   mvt_dev<var> out;
   for (size_t i = 0; i < p.size(); ++i) {
     out.val.push_back(node->val() + i * size_t(n));
-    out.adj.push_back(node->adj_ + i * size_t(n));
+    out.adj.push_back(node->adj() + i * size_t(n));
   }
   return out;
 }
@@ -770,12 +772,13 @@ inline std::conditional_t<internal::any_var<T_y, T_loc, T_covar>::value, var, do
   bool lower_only = false;
   double host_logdet = 0.0;
   if constexpr (std::is_same<T_covar, dev_var_matrix>::value) {
-    Ld = internal::operand(L);
     aux = L.vi_->aux_;
     lower_only = L.vi_->structure_ == dev_structure::lower;
+    // (a factor that takes the partials unexpanded: its dense adjoint may never be touched)
+    Ld = lower_only && L.vi_->sink_ ? internal::structured_operand(L) : internal::operand(L);
   } else {
     const internal::eig_in eL = internal::prepare(L);
-    Ld = internal::commit(eL);
+    Ld = internal::commit(eL, eL.node && eL.node->structure_ == dev_structure::lower && eL.node->sink_);
     if (Ld.vi) {
       aux = Ld.vi->aux_;
       lower_only = Ld.vi->structure_ == dev_structure::lower;

@@ -85,14 +85,16 @@ class multiply_lower_dev_vari : public device_vari {
   dev_matrix_vari* C_;
   multiply_lower_dev_vari(dev_matrix_vari* A, dev_matrix_vari* B)
       : device_vari(0.0), A_(A), B_(B), C_(new dev_matrix_vari(A->rows_, B->cols_, dev_structure::lower)) {
+    A->want_adjoint();
+    B->want_adjoint();
     const int n = A->rows_;
     amd::check(smg_multiply_lower_fwd(amd::ctx(), A_->val(), n, B_->val(), n, n, C_->raw_val(), n), "multiply");
   }
   void chain() override {
     const int n = A_->rows_;
     double* ws = amd::alloc_doubles(size_t(n) * n);
-    amd::check(smg_multiply_lower_rev(amd::ctx(), A_->val(), n, B_->val(), n, C_->adj_, n, n, A_->adj_, n,
-                                      B_->adj_, n, ws),
+    amd::check(smg_multiply_lower_rev(amd::ctx(), A_->val(), n, B_->val(), n, C_->adj(), n, n, A_->adj(), n,
+                                      B_->adj(), n, ws),
                "multiply");
   }
 };
@@ -107,14 +109,16 @@ class add_dev_vari : public device_vari {
   dev_matrix_vari* C_;
   add_dev_vari(dev_matrix_vari* A, dev_matrix_vari* B)
       : device_vari(0.0), A_(A), B_(B), C_(new dev_matrix_vari(A->rows_, A->cols_)) {
+    A->want_adjoint();
+    B->want_adjoint();
     smg_ctx* c = amd::ctx();
     amd::check(smg_copy_matrix(c, A->rows_, A->cols_, A->val(), A->rows_, C_->raw_val(), C_->rows_, 0, 0), "add");
     amd::check(smg_axpy(c, (long long)C_->size(), 1.0, B->val(), 1, C_->raw_val(), 1), "add");
   }
   void chain() override {
     smg_ctx* c = amd::ctx();
-    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, C_->adj_, 1, A_->adj_, 1), "add");
-    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, C_->adj_, 1, B_->adj_, 1), "add");
+    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, C_->adj(), 1, A_->adj(), 1), "add");
+    amd::check(smg_axpy(c, (long long)C_->size(), 1.0, C_->adj(), 1, B_->adj(), 1), "add");
   }
 };
 
@@ -125,12 +129,13 @@ class tril_dev_vari : public device_vari {
   dev_matrix_vari* C_;
   explicit tril_dev_vari(dev_matrix_vari* A)
       : device_vari(0.0), A_(A), C_(new dev_matrix_vari(A->rows_, A->cols_, dev_structure::lower)) {
+    A->want_adjoint();
     smg_ctx* c = amd::ctx();
     amd::zero(C_->raw_val(), C_->size());
     amd::check(smg_add_tril(c, A->rows_, A->cols_, 1.0, A->val(), A->rows_, C_->raw_val(), C_->rows_), "tril");
   }
   void chain() override {
-    amd::check(smg_add_tril(amd::ctx(), A_->rows_, A_->cols_, 1.0, C_->adj_, C_->rows_, A_->adj_, A_->rows_),
+    amd::check(smg_add_tril(amd::ctx(), A_->rows_, A_->cols_, 1.0, C_->adj(), C_->rows_, A_->adj(), A_->rows_),
                "tril");
   }
 };
@@ -142,10 +147,13 @@ class lse_tangent_dev_vari : public device_vari {
   dev_matrix_vari* xd_;
   double lse_;
   lse_tangent_dev_vari(double t, double lse, dev_matrix_vari* x, dev_matrix_vari* xd)
-      : device_vari(t), x_(x), xd_(xd), lse_(lse) {}
+      : device_vari(t), x_(x), xd_(xd), lse_(lse) {
+    x->want_adjoint();
+    xd->want_adjoint();
+  }
   void chain() override {
     amd::check(smg_lse_tangent_rev(amd::ctx(), x_->val(), xd_->val(), (long long)x_->size(), lse_, val_, adj_,
-                                   x_->adj_, xd_->adj_),
+                                   x_->adj(), xd_->adj()),
                "log_sum_exp");
   }
 };
@@ -163,10 +171,13 @@ class glm_tangent_dev_vari : public device_vari {
   glm_tangent_dev_vari(double t, dev_matrix_vari* eta, dev_matrix_vari* etad, vari* alpha, vari* alphad, double a,
                        double ad, const int* y)
       : device_vari(t), eta_(eta), etad_(etad), alpha_(alpha), alphad_(alphad), a_(a), ad_(ad), y_(y),
-        out2_(amd::alloc_doubles(2)) {}
+        out2_(amd::alloc_doubles(2)) {
+    eta->want_adjoint();
+    etad->want_adjoint();
+  }
   void chain() override {
     amd::check(smg_glm_tangent_rev(amd::ctx(), eta_->val(), a_, etad_->val(), ad_, y_, (long long)eta_->size(), adj_,
-                                   eta_->adj_, etad_->adj_, out2_),
+                                   eta_->adj(), etad_->adj(), out2_),
                "bernoulli_logit_glm_lpmf");
     if (alpha_) add_pending_adjoint(alpha_, out2_);
     if (alphad_) add_pending_adjoint(alphad_, out2_ + 1);
@@ -325,6 +336,8 @@ class chol_tangent_dev_vari : public device_vari {
   double* P_;
   chol_tangent_dev_vari(dev_matrix_vari* L, dev_matrix_vari* Ad)
       : device_vari(0.0), L_(L), Ad_(Ad), Ld_(new dev_matrix_vari(L->rows_, L->cols_, dev_structure::lower)) {
+    L->want_adjoint();
+    Ad->want_adjoint();
     const int n = L->rows_;
     const size_t nn = size_t(n) * n;
     Wt_ = amd::alloc_doubles(nn);
@@ -346,8 +359,8 @@ class chol_tangent_dev_vari : public device_vari {
   void chain() override {
     const int n = L_->rows_;
     double* ws = amd::alloc_doubles(2 * size_t(n) * n);
-    amd::check(smg_chol_tangent_rev(amd::ctx(), L_->val(), n, W_, Wt_, Y_, P_, n, Ld_->adj_, n, n, L_->adj_, n,
-                                    Ad_->adj_, n, ws),
+    amd::check(smg_chol_tangent_rev(amd::ctx(), L_->val(), n, W_, Wt_, Y_, P_, n, Ld_->adj(), n, n, L_->adj(), n,
+                                    Ad_->adj(), n, ws),
                "cholesky_decompose");
   }
 };
@@ -363,6 +376,9 @@ inline bool chol_tangent_composed() {
 inline dev_fvar_matrix cholesky_decompose(const dev_fvar_matrix& A) {
   dev_fvar_matrix L;
   if (!internal::chol_tangent_composed()) {
+    // (the tangent node's reverse adds into the adjoint of A's tangent: its
+    // zeroing is queued ahead of the factorisation, to run beside the first panel)
+    A.d_.vi_->want_adjoint();
     L.val_ = internal::cholesky_decompose_with_inverse(A.val_);  // checks + L (structurally lower), W = L^{-1}
     L.d_ = dev_var_matrix((new internal::chol_tangent_dev_vari(L.val_.vi_, A.d_.vi_))->Ld_);
     return L;

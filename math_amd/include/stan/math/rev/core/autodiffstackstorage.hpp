@@ -14,7 +14,8 @@
 // MI355X extension: matrix-valued nodes keep their values and adjoints in the
 // thread's device arena (stan/math/amd/device.hpp).  The tape therefore also
 // records
-//   dev_adj_stack_      device adjoint buffers (zeroed by set_zero_all_adjoints)
+//   dev_adj_stack_      device adjoint buffers (zeroed by set_zero_all_adjoints;
+//                       a large one is first zeroed when a dense user appears)
 //   nested_dev_marks_   device-arena marks per nesting level
 //   pending_            device -> host adjoint contributions that must land in
 //                       host vari::adj_ before the next host chain() runs.
@@ -35,6 +36,9 @@ class chainable_alloc;
 struct dev_buffer {
   double* ptr;
   size_t n;
+  // false: a large adjoint, registered unzeroed; zeroed when its first dense
+  // user appears (grad.hpp clear_device_adjoint)
+  bool cleared;
 };
 struct pending_adjoint {
   vari* target;       // host vari whose adj_ receives the value
@@ -112,6 +116,9 @@ struct AutodiffStackSingleton {
     // reverse sweeps started on this tape (grad()): a structured adjoint a
     // node deposits is valid for the sweep that deposited it only
     size_t sweep_ = 0;
+    // an adjoint zeroing was queued on the zeroing stream since the main
+    // stream last joined it (grad.hpp clear_device_adjoint)
+    bool dev_clear_queued_ = false;
     // after a sweep, publish_ (set once a host block exists: stan/math/amd/
     // matrix.hpp) writes every host block's device adjoint into its varis, so
     // they read what the reference's would; no_publish_ > 0 while a functional

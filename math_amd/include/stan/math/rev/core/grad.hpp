@@ -9,8 +9,9 @@
 //   set_zero_all_adjoints(_nested)  rev/core/set_zero_all_adjoints*.hpp
 //   empty_nested / nested_size
 // Device extension: the same calls mark / rewind the device arena, zero the
-// device adjoint buffers, and land pending device->host adjoint
-// contributions (flush_pending) before any host chain() that could read them.
+// device adjoint buffers (a large one when its first dense user appears), and
+// land pending device->host adjoint contributions (flush_pending) before any
+// host chain() that could read them.
 
 #include <stan/math/amd/device.hpp>
 #include <stan/math/rev/core/vari.hpp>
@@ -24,22 +25,48 @@
 namespace stan {
 namespace math {
 
-/** Register a device adjoint buffer with the tape (zeroed now and by
- * set_zero_all_adjoints).  A large buffer is zeroed on the context's zeroing
- * stream, overlapping the rest of the forward pass; only a reverse sweep (or
- * a host read of the adjoint) touches it, and both join that stream first
- * (join_device_adjoints). */
-inline void register_device_adjoint(double* p, size_t n) {
-  if (n >= (size_t(1) << 17))
-    amd::check(smg_memset_async(amd::ctx(), p, n * sizeof(double)), "zero");
-  else
-    amd::zero(p, n);
-  ChainableStack::instance_->dev_adj_stack_.push_back({p, n});
+/** Register a device adjoint buffer with the tape; returns its slot in
+ * dev_adj_stack_.  A small buffer is zeroed now.  A large one is registered
+ * unzeroed: under a structured reverse (the closed form of cholesky_decompose
+ * under multi_normal_cholesky_lpdf, rev/fun/cholesky_decompose.hpp) the N^2
+ * adjoints of a GP's K, K + dI and L are neither written nor read, so the
+ * zeroing waits for the buffer's first dense user (clear_device_adjoint). */
+inline size_t register_device_adjoint(double* p, size_t n) {
+  const bool large = n >= (size_t(1) << 17);
+  if (!large) amd::zero(p, n);
+  auto& s = ChainableStack::instance_->dev_adj_stack_;
+  s.push_back({p, n, !large});
+  return s.size() - 1;
 }
 
 /** The main stream waits for every adjoint zeroing still in flight. */
 inline void join_device_adjoints() {
   if (amd::has_ctx()) amd::check(smg_join_async(amd::ctx()), "grad");
+  ChainableStack::instance_->dev_clear_queued_ = false;
+}
+
+/** Zero the adjoint buffer in `slot` unless that has happened.
+ * now == false (dev_matrix_vari::want_adjoint(), by the constructor of a node
+ * whose chain() will add into the buffer): the zeroing is queued on the
+ * context's zeroing stream, overlapping the rest of the forward pass; only a
+ * reverse sweep (or a host read of the adjoint) touches the buffer, and both
+ * join that stream first.  now == true (dev_matrix_vari::adj(), by whatever
+ * is about to add into the buffer or read it on the main stream): zeroed on
+ * the main stream, in front of that user; a zeroing still queued is joined. */
+inline void clear_device_adjoint(size_t slot, bool now) {
+  auto* st = ChainableStack::instance_;
+  dev_buffer& b = st->dev_adj_stack_[slot];
+  if (b.cleared) {
+    if (now && st->dev_clear_queued_) join_device_adjoints();
+    return;
+  }
+  b.cleared = true;
+  if (now) {
+    amd::zero(b.ptr, b.n);
+  } else {
+    amd::check(smg_memset_async(amd::ctx(), b.ptr, b.n * sizeof(double)), "zero");
+    st->dev_clear_queued_ = true;
+  }
 }
 
 /** Queue target->adj_ += *src (src: device scalar) for the next flush. */
@@ -239,7 +266,10 @@ static inline void set_zero_all_adjoints() {
   ++st->sweep_;  // (a structured adjoint of the last sweep is gone with the dense ones)
   for (auto* v : st->var_stack_) v->set_zero_adjoint();
   for (auto* v : st->var_nochain_stack_) v->set_zero_adjoint();
-  for (auto& b : st->dev_adj_stack_) amd::zero(b.ptr, b.n);
+  for (auto& b : st->dev_adj_stack_) {
+    amd::zero(b.ptr, b.n);
+    b.cleared = true;
+  }
   zero_host_blocks(0);
   st->pending_.clear();
 }
@@ -256,8 +286,10 @@ static inline void set_zero_all_adjoints_nested() {
   const size_t s2 = st->nested_var_nochain_stack_sizes_.back();
   for (size_t i = (s2 == 0U) ? 0U : (s2 - 1); i < st->var_nochain_stack_.size(); ++i)
     st->var_nochain_stack_[i]->set_zero_adjoint();
-  for (size_t i = st->nested_dev_adj_sizes_.back(); i < st->dev_adj_stack_.size(); ++i)
+  for (size_t i = st->nested_dev_adj_sizes_.back(); i < st->dev_adj_stack_.size(); ++i) {
     amd::zero(st->dev_adj_stack_[i].ptr, st->dev_adj_stack_[i].n);
+    st->dev_adj_stack_[i].cleared = true;
+  }
   zero_host_blocks(st->nested_host_block_sizes_.back());
   st->pending_.clear();
 }

@@ -81,7 +81,7 @@ class glm_dev_vari : public local_adjoint_vari {
     if (beta_vi_)
       for (int j = 0; j < M_; ++j) beta_vi_[j]->adj_ += adj_ * g_[1 + j];
     if (beta_dev_)
-      amd::check(smg_axpy(amd::ctx(), M_, adj_, g_dev_, 1, beta_dev_->adj_, 1),
+      amd::check(smg_axpy(amd::ctx(), M_, adj_, g_dev_, 1, beta_dev_->adj(), 1),
                  "bernoulli_logit_glm_lpmf");
   }
 };

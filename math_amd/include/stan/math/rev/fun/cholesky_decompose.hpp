@@ -57,6 +57,10 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
         dadj_(d_vi ? amd::alloc_doubles(1) : nullptr), dv_(dv),
         pos_(ChainableStack::instance_->var_stack_.size() - 1), d_(d), src_{} {
     if (A.rows == A.cols && !dv.rows) B_->sink_ = this;  // (square, scalar diagonal)
+    // chain() adds into A's dense adjoint unless B's adjoint arrives in
+    // inverse form and A's producer takes it too: only then may A's stay
+    // unzeroed until someone reads it
+    if (A_.vi && !(B_->sink_ == this && A_.vi->sink_)) A_.vi->want_adjoint();
     // a scalar diagonal on a GP covariance (its values formed or not): B's
     // values wait for their first reader -- none under cholesky_decompose,
     // which generates them into its factor's buffer (chol_source)
@@ -89,6 +93,12 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
   bool may_write_device_adjoint(const void* node) const override {
     return (A_.vi && node == A_.vi) || (dv_.vi && node == dv_.vi);
   }
+  // B's adjoint will be dense: chain() then adds it into A's
+  void expect_dense_adjoint() override {
+    if (!A_.vi) return;
+    A_.vi->want_adjoint();
+    if (A_.vi->sink_) A_.vi->sink_->expect_dense_adjoint();
+  }
   // one deposit per sweep (a second factorisation of B writes its G densely)
   bool take_inverse_adjoint(const inverse_adjoint& d, double*) override {
     if (B_->sink_ != this) return false;
@@ -100,9 +110,9 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
   // or not yet chained (dep_), as gp_exp_quad_cov_dev_vari::expand_adjoint
   void expand_adjoint() override {
     const size_t sw = ChainableStack::instance_->sweep_;
-    if (exp_.C && exp_.sweep == sw) exp_.expand_into(B_->adj_);
+    if (exp_.C && exp_.sweep == sw) exp_.expand_into(B_->adj());
     exp_ = inverse_adjoint{};
-    if (dep_.C && dep_.sweep == sw) dep_.expand_into(B_->adj_);
+    if (dep_.C && dep_.sweep == sw) dep_.expand_into(B_->adj());
     dep_ = inverse_adjoint{};
   }
 
@@ -132,17 +142,17 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
         exp_ = d;
         return;
       }
-      d.expand_into(B_->adj_);  // another node wrote B's adjoint too: the dense sum
+      d.expand_into(B_->adj());  // another node wrote B's adjoint too: the dense sum
     }
     double* dadj = dv_.rows ? dv_.adj() : dadj_;
     if (dadj_) amd::check(smg_memset(c, dadj_, 0, sizeof(double)), "add_diag");
     const int vec = dv_.rows ? 1 : 0;
     if (m == n) {
-      amd::check(smg_add_diag_rev(c, B_->adj_, m, m, A_.adj(), m, dadj, vec), "add_diag");
+      amd::check(smg_add_diag_rev(c, B_->adj(), m, m, A_.adj(), m, dadj, vec), "add_diag");
     } else {
       if (A_.adj())
-        amd::check(smg_axpy(c, (long long)m * n, 1.0, B_->adj_, 1, A_.adj(), 1), "add_diag");
-      amd::check(smg_add_diag_rev(c, B_->adj_, m, k, nullptr, 0, dadj, vec), "add_diag");
+        amd::check(smg_axpy(c, (long long)m * n, 1.0, B_->adj(), 1, A_.adj(), 1), "add_diag");
+      amd::check(smg_add_diag_rev(c, B_->adj(), m, k, nullptr, 0, dadj, vec), "add_diag");
     }
     if (d_vi_) add_pending_adjoint(d_vi_, dadj_);
   }
@@ -150,7 +160,7 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
 
 /**
  * The factor's adjoint reaches this node in one of two forms:
- *  - dense (L_->adj_): Murray's blocked reverse, like the reference's chain()
+ *  - dense (L's adjoint buffer): Murray's blocked reverse, like the reference's chain()
  *    (rev/mat/fun/cholesky_decompose.hpp:118-166);
  *  - structured: a multi_normal_cholesky_lpdf consuming the factor deposits
  *    its partials unexpanded (take_mvn_adjoint) instead of writing the dense
@@ -158,7 +168,7 @@ class add_diag_dev_vari : public device_vari, public structured_adjoint_sink, pu
  *    one wrote the factor's adjoint (may_write_device_adjoint), the reverse is
  *    the closed form Abar += adj Phi(s s^T - K^{-1}) (smg_cholesky_mvn_rev:
  *    the same 2N^3/3 in a few large GEMMs); otherwise the deposit is expanded
- *    into L_->adj_ first and Murray's reverse runs on the sum.
+ *    into L's adjoint first and Murray's reverse runs on the sum.
  */
 class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
  public:
@@ -188,7 +198,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
   void expand(const double* ws, double adj, int k) const {
     for (int o = 0; o < k; ++o)
       amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->raw_val(), n_, L_->aux_, n_, ws + 2 * size_t(n_) * o, adj, 1, nullptr,
-                                      nullptr, L_->adj_, n_),
+                                      nullptr, L_->adj(), n_),
                  "cholesky_decompose");
   }
 
@@ -323,7 +333,7 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
         d.ss = 2LL * n_;
         d.adj = dep_adj_;
         d.sweep = st->sweep_;
-        if (!(A_->sink_ && A_->sink_->take_inverse_adjoint(d, nullptr))) d.expand_into(A_->adj_);
+        if (!(A_->sink_ && A_->sink_->take_inverse_adjoint(d, nullptr))) d.expand_into(A_->adj());
         return;
       }
       // expand the deposit: the MVN's own lower-only partials, added densely
@@ -332,8 +342,8 @@ class cholesky_dev_vari : public device_vari, public structured_adjoint_sink {
     if (!deposit) record(false);
     // Murray's algorithm overwrites its input and reads only its lower triangle
     double* work = amd::alloc_doubles(nn);
-    amd::check(smg_copy_tril(c, n_, n_, L_->adj_, n_, work, n_), "cholesky_decompose");
-    amd::check(smg_cholesky_rev(c, L_->raw_val(), n_, L_->aux_, work, n_, n_, A_->adj_, n_),
+    amd::check(smg_copy_tril(c, n_, n_, L_->adj(), n_, work, n_), "cholesky_decompose");
+    amd::check(smg_cholesky_rev(c, L_->raw_val(), n_, L_->aux_, work, n_, n_, A_->adj(), n_),
                "cholesky_decompose");
   }
 };
@@ -376,10 +386,10 @@ inline dev_var_matrix add_diag_dev(const dev_operand& A, double d, vari* d_vi, c
 /** add_diag(mat, to_add) (prim/mat/fun/add_diag.hpp:20-55) on device operands:
  * a scalar or a vector to_add, any var / data combination, rectangular mat. */
 inline dev_var_matrix add_diag(const dev_var_matrix& A, const var& d) {
-  return internal::add_diag_dev(internal::operand(A), d.val(), d.vi_, {});
+  return internal::add_diag_dev(internal::structured_operand(A), d.val(), d.vi_, {});
 }
 inline dev_var_matrix add_diag(const dev_var_matrix& A, double d) {
-  return internal::add_diag_dev(internal::operand(A), d, nullptr, {});
+  return internal::add_diag_dev(internal::structured_operand(A), d, nullptr, {});
 }
 inline dev_var_matrix add_diag(const dev_data<double>& A, const var& d) {
   return internal::add_diag_dev(internal::operand(A), d.val(), d.vi_, {});
@@ -423,6 +433,18 @@ inline dev_var_matrix cholesky_decompose_impl(const dev_var_matrix& A, var* host
   L->aux_ = amd::alloc_doubles(size_t(smg_cholesky_aux_doubles(n)));
   // the node's tape position once pushed (cholesky_dev_vari::pos_)
   const size_t pos = ChainableStack::instance_->var_stack_.size();
+  // The closed-form reverse touches neither A's nor L's dense adjoint.  Where
+  // it cannot apply -- switched off, refused at this position last time (the
+  // factor's adjoint had other writers), or A's producer takes no inverse
+  // form -- Murray's reverse will read L's and add into A's: their zeroing is
+  // queued now, to run beside the first panel, not in front of that reverse.
+  {
+    const bool dense = !internal::cholesky_dev_vari::closed_form_enabled() ||
+                       internal::cholesky_dev_vari::history_of(pos, n) == 0;
+    if (dense || !A.vi_->sink_) A.vi_->want_adjoint();
+    if (dense && A.vi_->sink_) A.vi_->sink_->expect_dense_adjoint();
+    if (dense) L->want_adjoint();
+  }
   double* inv_ws = nullptr;
   // want_w: W = L^{-1} alone, progressively (the HVP's value factor, whose
   // tangent node reads W); n % 512 == 0 and n >= 1024, else not formed

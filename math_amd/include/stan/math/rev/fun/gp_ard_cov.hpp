@@ -132,9 +132,9 @@ class gp_ard_cov_dev_vari : public device_vari, public structured_adjoint_sink, 
 
   void expand_adjoint() override {
     const size_t sw = ChainableStack::instance_->sweep_;
-    if (exp_.C && exp_.sweep == sw) exp_.expand_into(K_->adj_);
+    if (exp_.C && exp_.sweep == sw) exp_.expand_into(K_->adj());
     exp_ = inverse_adjoint{};
-    if (dep_.C && dep_.sweep == sw) dep_.expand_into(K_->adj_);
+    if (dep_.C && dep_.sweep == sw) dep_.expand_into(K_->adj());
     dep_ = inverse_adjoint{};
   }
 
@@ -148,12 +148,12 @@ class gp_ard_cov_dev_vari : public device_vari, public structured_adjoint_sink, 
         exp_ = d;
         return;
       }
-      d.expand_into(K_->adj_);  // another node wrote K's adjoint too: the dense sum
+      d.expand_into(K_->adj());  // another node wrote K's adjoint too: the dense sum
     }
     if (!wants_out()) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out_, 0, size_t(1 + D_) * sizeof(double)), fn_);
-    amd::check(smg_gp_ard_cov_rev(c, family_, zt_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out_), fn_);
+    amd::check(smg_gp_ard_cov_rev(c, family_, zt_, D_, n_, sigma_d_, l_d_, K_->adj(), n_, out_), fn_);
     deposit_out();
   }
 };

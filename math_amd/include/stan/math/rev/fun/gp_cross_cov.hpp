@@ -83,7 +83,7 @@ class gp_cross_cov_dev_vari : public device_vari {
     if (!sigma_vi_ && !l_vi_) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out2_, 0, 2 * sizeof(double)), fn_);
-    amd::check(smg_gp_cross_cov_rev(c, family_, x1_, n1_, x2_, n2_, D_, sigma_d_, l_d_, K_->adj_, n1_, out2_), fn_);
+    amd::check(smg_gp_cross_cov_rev(c, family_, x1_, n1_, x2_, n2_, D_, sigma_d_, l_d_, K_->adj(), n1_, out2_), fn_);
     if (sigma_vi_) add_pending_adjoint(sigma_vi_, out2_);
     if (l_vi_) add_pending_adjoint(l_vi_, out2_ + 1);
   }
@@ -141,7 +141,7 @@ class gp_ard_cross_cov_dev_vari : public device_vari {
     if (!sigma_vi_ && !l_vis_) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out_, 0, size_t(1 + D_) * sizeof(double)), fn_);
-    amd::check(smg_gp_ard_cross_cov_rev(c, family_, z1t_, n1_, z2t_, n2_, D_, sigma_d_, l_d_, K_->adj_, n1_, out_), fn_);
+    amd::check(smg_gp_ard_cross_cov_rev(c, family_, z1t_, n1_, z2t_, n2_, D_, sigma_d_, l_d_, K_->adj(), n1_, out_), fn_);
     if (sigma_vi_) add_pending_adjoint(sigma_vi_, out_);
     if (l_vis_)
       for (int d = 0; d < D_; ++d) add_pending_adjoint(l_vis_[d], out_ + 1 + d);

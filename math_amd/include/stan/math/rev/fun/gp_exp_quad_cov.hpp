@@ -133,9 +133,9 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
   // this node's turn -- chain() then takes the dense path on the sum)
   void expand_adjoint() override {
     const size_t sw = ChainableStack::instance_->sweep_;
-    if (exp_.C && exp_.sweep == sw) exp_.expand_into(K_->adj_);
+    if (exp_.C && exp_.sweep == sw) exp_.expand_into(K_->adj());
     exp_ = inverse_adjoint{};
-    if (dep_.C && dep_.sweep == sw) dep_.expand_into(K_->adj_);
+    if (dep_.C && dep_.sweep == sw) dep_.expand_into(K_->adj());
     dep_ = inverse_adjoint{};
   }
 
@@ -150,14 +150,14 @@ class gp_exp_quad_cov_dev_vari : public device_vari, public structured_adjoint_s
         exp_ = d;
         return;
       }
-      d.expand_into(K_->adj_);  // another node wrote K's adjoint too: the dense sum
+      d.expand_into(K_->adj());  // another node wrote K's adjoint too: the dense sum
     }
     if (!sigma_vi_ && !l_vi_) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out2_, 0, 2 * sizeof(double)), fn_);
     amd::check(family_ == SMG_GP_EXP_QUAD
-                   ? smg_gp_exp_quad_cov_nd_rev(c, x_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out2_)
-                   : smg_gp_cov_rev(c, family_, x_, D_, n_, sigma_d_, l_d_, K_->adj_, n_, out2_),
+                   ? smg_gp_exp_quad_cov_nd_rev(c, x_, D_, n_, sigma_d_, l_d_, K_->adj(), n_, out2_)
+                   : smg_gp_cov_rev(c, family_, x_, D_, n_, sigma_d_, l_d_, K_->adj(), n_, out2_),
                fn_);
     if (sigma_vi_) add_pending_adjoint(sigma_vi_, out2_);
     if (l_vi_) add_pending_adjoint(l_vi_, out2_ + 1);

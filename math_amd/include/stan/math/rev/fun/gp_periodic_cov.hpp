@@ -94,7 +94,7 @@ class gp_periodic_cov_dev_vari : public device_vari {
     if (!sigma_vi_ && !l_vi_ && !p_vi_) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out3_, 0, 3 * sizeof(double)), fn_);
-    amd::check(smg_gp_periodic_cov_rev(c, x1_, n1_, x2_, n2_, D_, sigma_d_, l_d_, p_d_, K_->adj_, n1_, out3_), fn_);
+    amd::check(smg_gp_periodic_cov_rev(c, x1_, n1_, x2_, n2_, D_, sigma_d_, l_d_, p_d_, K_->adj(), n1_, out3_), fn_);
     if (sigma_vi_) add_pending_adjoint(sigma_vi_, out3_);
     if (l_vi_) add_pending_adjoint(l_vi_, out3_ + 1);
     if (p_vi_) add_pending_adjoint(p_vi_, out3_ + 2);
@@ -129,7 +129,7 @@ class gp_dot_prod_cov_dev_vari : public device_vari {
     if (!sigma_vi_) return;
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out1_, 0, sizeof(double)), fn_);
-    amd::check(smg_gp_dot_prod_cov_rev(c, n1_, n2_, sigma_d_, K_->adj_, n1_, out1_), fn_);
+    amd::check(smg_gp_dot_prod_cov_rev(c, n1_, n2_, sigma_d_, K_->adj(), n1_, out1_), fn_);
     add_pending_adjoint(sigma_vi_, out1_);
   }
 };

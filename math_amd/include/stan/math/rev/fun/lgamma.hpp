@@ -38,6 +38,7 @@ class unary_special_dev_vari : public device_vari {
   dev_matrix_vari* y_;
   explicit unary_special_dev_vari(dev_matrix_vari* x)
       : device_vari(0.0), x_(x), y_(new dev_matrix_vari(x->rows_, x->cols_)) {
+    x->want_adjoint();
     const long long n = (long long)x_->size();
     amd::check(OP == 0 ? smg_lgamma_fwd(amd::ctx(), x_->val(), n, y_->raw_val())
                        : smg_digamma_fwd(amd::ctx(), x_->val(), n, y_->raw_val()),
@@ -45,8 +46,8 @@ class unary_special_dev_vari : public device_vari {
   }
   void chain() override {
     const long long n = (long long)x_->size();
-    amd::check(OP == 0 ? smg_lgamma_rev(amd::ctx(), x_->val(), n, y_->adj_, x_->adj_)
-                       : smg_digamma_rev(amd::ctx(), x_->val(), n, y_->adj_, x_->adj_),
+    amd::check(OP == 0 ? smg_lgamma_rev(amd::ctx(), x_->val(), n, y_->adj(), x_->adj())
+                       : smg_digamma_rev(amd::ctx(), x_->val(), n, y_->adj(), x_->adj()),
                OP == 0 ? "lgamma" : "digamma");
   }
 };

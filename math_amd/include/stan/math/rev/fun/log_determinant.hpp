@@ -24,12 +24,14 @@ class log_determinant_dev_vari : public device_vari {
   double* LU_;
   int* piv_;
   log_determinant_dev_vari(double v, dev_matrix_vari* A, double* LU, int* piv)
-      : device_vari(v), A_(A), LU_(LU), piv_(piv) {}
+      : device_vari(v), A_(A), LU_(LU), piv_(piv) {
+    A->want_adjoint();
+  }
   void chain() override {
     const int n = A_->rows_;
     double* ws = amd::alloc_doubles(3 * size_t(n) * n);
     int* iws = amd::alloc_ints(size_t(n));
-    amd::check(smg_log_determinant_rev(amd::ctx(), LU_, piv_, n, adj_, A_->adj_, n, ws, iws), "log_determinant");
+    amd::check(smg_log_determinant_rev(amd::ctx(), LU_, piv_, n, adj_, A_->adj(), n, ws, iws), "log_determinant");
   }
 };
 

@@ -20,10 +20,12 @@ namespace internal {
 class log_sum_exp_dev_vari : public device_vari {
  public:
   dev_matrix_vari* x_;
-  log_sum_exp_dev_vari(double v, dev_matrix_vari* x) : device_vari(v), x_(x) {}
+  log_sum_exp_dev_vari(double v, dev_matrix_vari* x) : device_vari(v), x_(x) {
+    x->want_adjoint();
+  }
   void chain() override {
     amd::check(smg_log_sum_exp_rev(amd::ctx(), x_->val(), (long long)x_->size(), val_, adj_,
-                                   x_->adj_),
+                                   x_->adj()),
                "log_sum_exp");
   }
 };

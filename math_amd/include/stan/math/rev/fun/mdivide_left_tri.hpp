@@ -48,13 +48,13 @@ class mdivide_left_tri_dev_vari : public device_vari {
     double* ws = amd::alloc_doubles(size_t(m) * n);
     if (W_) {  // ws = W^T Cadj;  Aadj (lower) -= ws C^T;  Badj += ws  (:104-123)
       smg_ctx* c = amd::ctx();
-      amd::check(smg_trmv_inv(c, 1, W_, A_.rows, m, C_->adj_, ws), "mdivide_left_tri");
+      amd::check(smg_trmv_inv(c, 1, W_, A_.rows, m, C_->adj(), ws), "mdivide_left_tri");
       if (A_.adj()) amd::check(smg_rank1_lower(c, m, -1.0, ws, C_->raw_val(), A_.adj(), A_.rows), "mdivide_left_tri");
       if (B_.adj()) amd::check(smg_axpy(c, (long long)m, 1.0, ws, 1, B_.adj(), 1), "mdivide_left_tri");
       return;
     }
     amd::check(smg_mdivide_left_tri_aux_rev(amd::ctx(), lower_, A_.val(), A_.rows, aux(), C_->raw_val(), m,
-                                            C_->adj_, m, m, n, A_.adj(), A_.rows, B_.adj(), m, ws),
+                                            C_->adj(), m, m, n, A_.adj(), A_.rows, B_.adj(), m, ws),
                "mdivide_left_tri");
   }
 };

@@ -39,7 +39,13 @@ class mvn_cholesky_dev_vari : public device_vari {
 
   mvn_cholesky_dev_vari(double lp, dev_matrix_vari* L, const double* ws,
                         dev_matrix_vari* y = nullptr, dev_matrix_vari* mu = nullptr)
-      : device_vari(lp), L_(L), ws_(ws), n_(L->rows_), y_(y), mu_(mu) {}
+      : device_vari(lp), L_(L), ws_(ws), n_(L->rows_), y_(y), mu_(mu) {
+    // chain() writes L's dense adjoint unless L's producer takes the partials
+    // unexpanded; y's and mu's always
+    if (!(L->structure_ == dev_structure::lower && L->sink_)) L->want_adjoint();
+    if (y) y->want_adjoint();
+    if (mu) mu->want_adjoint();
+  }
 
   bool may_write_device_adjoint(const void* node) const override {
     return (node == L_ && !deposited_) || (y_ && node == y_) || (mu_ && node == mu_);
@@ -51,8 +57,8 @@ class mvn_cholesky_dev_vari : public device_vari {
     // (rev/fun/cholesky_decompose.hpp: its reverse then has a closed form)
     deposited_ = lower_only && L_->sink_ && L_->sink_->take_mvn_adjoint(this, ws_, adj_);
     amd::check(smg_mvn_cholesky_rev(amd::ctx(), L_->val(), n_, L_->aux_, n_, ws_, adj_, lower_only,
-                                    y_ ? y_->adj_ : nullptr, mu_ ? mu_->adj_ : nullptr,
-                                    deposited_ ? nullptr : L_->adj_, n_),
+                                    y_ ? y_->adj() : nullptr, mu_ ? mu_->adj() : nullptr,
+                                    deposited_ ? nullptr : L_->adj(), n_),
                "multi_normal_cholesky_lpdf");
   }
 };
@@ -198,7 +204,7 @@ inline vari* mvn_cholesky_multi(const dev_operand& L, const double* aux, bool lo
   if (!include_const) lp -= -std::log(std::sqrt(2.0 * 3.14159265358979323846)) * n * k;
   if (!include_logdet) lp -= host_logdet * k;
   *lp_out = lp;
-  bool any_adj = L.adj() != nullptr;
+  bool any_adj = L.vi != nullptr;
   for (int i = 0; i < k; ++i) any_adj = any_adj || obs[i].yadj || obs[i].muadj;
   if (!any_adj) return nullptr;
   return new mvn_multi_dev_vari(lp, L, aux, lower_only ? 1 : 0, ws, obs, k);

@@ -94,10 +94,10 @@ class multiply_dev_vari : public device_vari {
     smg_ctx* c = amd::ctx();
     if (lowvec_) {  // Aadj (lower) += Cadj b^T;  badj += A^T Cadj
       const int m = A_.rows;
-      if (A_.adj()) amd::check(smg_rank1_lower(c, m, 1.0, C_->adj_, B_.val(), A_.adj(), m), "multiply");
+      if (A_.adj()) amd::check(smg_rank1_lower(c, m, 1.0, C_->adj(), B_.val(), A_.adj(), m), "multiply");
       if (B_.adj()) {
         double* t = amd::alloc_doubles(size_t(m));
-        amd::check(smg_trmv_inv(c, 1, A_.val(), A_.rows, m, C_->adj_, t), "multiply");
+        amd::check(smg_trmv_inv(c, 1, A_.val(), A_.rows, m, C_->adj(), t), "multiply");
         amd::check(smg_axpy(c, (long long)m, 1.0, t, 1, B_.adj(), 1), "multiply");
       }
       return;
@@ -105,13 +105,13 @@ class multiply_dev_vari : public device_vari {
     if (gram_) {
       const int m = C_->rows_;
       double* S = amd::alloc_doubles(size_t(m) * m);  // Cadj + Cadj^T
-      amd::check(smg_memcpy_d2d(c, S, C_->adj_, size_t(m) * m * sizeof(double)), "multiply");
-      amd::check(smg_transpose(c, m, m, C_->adj_, m, S, m, 1.0), "multiply");
+      amd::check(smg_memcpy_d2d(c, S, C_->adj(), size_t(m) * m * sizeof(double)), "multiply");
+      amd::check(smg_transpose(c, m, m, C_->adj(), m, S, m, 1.0), "multiply");
       amd::check(smg_gemm(c, 0, 0, 0, m, A_.cols, m, 1.0, S, m, A_.val(), A_.rows, 1.0, A_.adj(), A_.rows),
                  "multiply");
       return;
     }
-    amd::check(smg_multiply_rev(c, A_.val(), A_.rows, B_.val(), B_.rows, C_->adj_, C_->rows_, A_.rows, A_.cols,
+    amd::check(smg_multiply_rev(c, A_.val(), A_.rows, B_.val(), B_.rows, C_->adj(), C_->rows_, A_.rows, A_.cols,
                                 B_.cols, A_.adj(), A_.rows, B_.adj(), B_.rows),
                "multiply");
   }
@@ -135,10 +135,10 @@ class scale_dev_vari : public device_vari {
   void chain() override {
     smg_ctx* x = amd::ctx();
     const long long n = (long long)A_.rows * A_.cols;
-    if (A_.adj()) amd::check(smg_axpy(x, n, c_, B_->adj_, 1, A_.adj(), 1), "multiply");
+    if (A_.adj()) amd::check(smg_axpy(x, n, c_, B_->adj(), 1, A_.adj(), 1), "multiply");
     if (c_vi_) {
       amd::check(smg_memset(x, cadj_, 0, sizeof(double)), "multiply");
-      amd::check(smg_dot(x, B_->adj_, A_.val(), n, cadj_), "multiply");
+      amd::check(smg_dot(x, B_->adj(), A_.val(), n, cadj_), "multiply");
       add_pending_adjoint(c_vi_, cadj_);
     }
   }
@@ -150,13 +150,14 @@ class transpose_dev_vari : public device_vari {
   dev_matrix_vari* B_;
   explicit transpose_dev_vari(dev_matrix_vari* A)
       : device_vari(0.0), A_(A), B_(new dev_matrix_vari(A->cols_, A->rows_)) {
+    A->want_adjoint();
     B_->transpose_of_ = A;
     amd::check(smg_transpose(amd::ctx(), A_->rows_, A_->cols_, A_->val(), A_->rows_, B_->raw_val(),
                              B_->rows_, 0.0),
                "transpose");
   }
   void chain() override {
-    amd::check(smg_transpose(amd::ctx(), B_->rows_, B_->cols_, B_->adj_, B_->rows_, A_->adj_,
+    amd::check(smg_transpose(amd::ctx(), B_->rows_, B_->cols_, B_->adj(), B_->rows_, A_->adj(),
                              A_->rows_, 1.0),
                "transpose");
   }
@@ -165,10 +166,12 @@ class transpose_dev_vari : public device_vari {
 class sum_dev_vari : public device_vari {
  public:
   dev_matrix_vari* A_;
-  sum_dev_vari(double v, dev_matrix_vari* A) : device_vari(v), A_(A) {}
+  sum_dev_vari(double v, dev_matrix_vari* A) : device_vari(v), A_(A) {
+    A->want_adjoint();
+  }
   void chain() override {
     const int uplo = A_->structure_ == dev_structure::lower ? 1 : 0;
-    amd::check(smg_shift(amd::ctx(), A_->rows_, A_->cols_, adj_, A_->adj_, A_->rows_, uplo), "sum");
+    amd::check(smg_shift(amd::ctx(), A_->rows_, A_->cols_, adj_, A_->adj(), A_->rows_, uplo), "sum");
   }
 };
 

@@ -59,7 +59,7 @@ class glm_sigma_dev_vari : public local_adjoint_vari {
     if (beta_vi_)
       for (int j = 0; j < M_; ++j) beta_vi_[j]->adj_ += adj_ * g_[1 + j];
     if (beta_dev_)
-      amd::check(smg_axpy(amd::ctx(), M_, adj_, g_dev_, 1, beta_dev_->adj_, 1), "normal_id_glm_lpdf");
+      amd::check(smg_axpy(amd::ctx(), M_, adj_, g_dev_, 1, beta_dev_->adj(), 1), "normal_id_glm_lpdf");
     if (sigma_vi_) sigma_vi_->adj_ += adj_ * g_[M_ + 1];
   }
 };

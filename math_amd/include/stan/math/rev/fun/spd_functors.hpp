@@ -85,7 +85,7 @@ class mdivide_left_spd_dev_vari : public device_vari {
     const int m = B_.rows, n = B_.cols;
     if (!A_.adj() && !B_.adj()) return;
     double* ws = amd::alloc_doubles(size_t(m) * n);
-    amd::check(smg_mdivide_left_spd_rev(amd::ctx(), L_, aux_, m, n, C_->raw_val(), m, C_->adj_, m, A_.adj(), m,
+    amd::check(smg_mdivide_left_spd_rev(amd::ctx(), L_, aux_, m, n, C_->raw_val(), m, C_->adj(), m, A_.adj(), m,
                                         B_.adj(), m, ws),
                "mdivide_left_spd");
   }
@@ -105,11 +105,13 @@ class log_determinant_spd_dev_vari : public device_vari {
   double* L_;
   double* aux_;
   log_determinant_spd_dev_vari(double v, dev_matrix_vari* A, double* L, double* aux)
-      : device_vari(v), A_(A), L_(L), aux_(aux) {}
+      : device_vari(v), A_(A), L_(L), aux_(aux) {
+    A->want_adjoint();
+  }
   void chain() override {
     const int n = A_->rows_;
     double* ws = amd::alloc_doubles(size_t(n) * n);
-    amd::check(smg_log_determinant_spd_rev(amd::ctx(), L_, aux_, n, adj_, A_->adj_, n, ws),
+    amd::check(smg_log_determinant_spd_rev(amd::ctx(), L_, aux_, n, adj_, A_->adj(), n, ws),
                "log_determinant_spd");
   }
 };
@@ -121,6 +123,7 @@ class mlt_self_transpose_dev_vari : public device_vari {
   dev_matrix_vari* C_;
   explicit mlt_self_transpose_dev_vari(dev_matrix_vari* L)
       : device_vari(0.0), L_(L), C_(new dev_matrix_vari(L->rows_, L->rows_)) {
+    L->want_adjoint();
     const int K = L->rows_, J = L->cols_;
     double* ws = amd::alloc_doubles(size_t(K) * (J > 0 ? J : 1));
     amd::check(smg_multiply_lower_tri_self_transpose_fwd(amd::ctx(), L_->val(), K, K, J, C_->raw_val(), K, ws),
@@ -129,8 +132,8 @@ class mlt_self_transpose_dev_vari : public device_vari {
   void chain() override {
     const int K = L_->rows_, J = L_->cols_;
     double* ws = amd::alloc_doubles(size_t(2) * K * J + size_t(K) * K);
-    amd::check(smg_multiply_lower_tri_self_transpose_rev(amd::ctx(), L_->val(), K, K, J, C_->adj_, K,
-                                                         L_->adj_, K, ws),
+    amd::check(smg_multiply_lower_tri_self_transpose_rev(amd::ctx(), L_->val(), K, K, J, C_->adj(), K,
+                                                         L_->adj(), K, ws),
                "multiply_lower_tri_self_transpose");
   }
 };
@@ -153,7 +156,7 @@ class quad_form_sym_dev_vari : public device_vari {
     const int M = B_.rows, N = B_.cols;
     if (!A_.adj() && !B_.adj()) return;
     double* ws = amd::alloc_doubles(size_t(M) * N + size_t(N) * N);
-    amd::check(smg_quad_form_sym_rev(amd::ctx(), A_.val(), M, B_.val(), M, M, N, C_->adj_, N, sym_adj_,
+    amd::check(smg_quad_form_sym_rev(amd::ctx(), A_.val(), M, B_.val(), M, M, N, C_->adj(), N, sym_adj_,
                                      A_.adj(), M, B_.adj(), M, ws),
                "quad_form_sym");
   }

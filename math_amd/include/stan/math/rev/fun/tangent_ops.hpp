@@ -36,7 +36,7 @@ class gp_tangent_dev_vari : public device_vari {
   void chain() override {
     smg_ctx* c = amd::ctx();
     amd::check(smg_memset(c, out4_, 0, 4 * sizeof(double)), "gp_exp_quad_cov");
-    amd::check(smg_gp_exp_quad_cov_tangent_rev(c, x_, n_, s_, l_, ds_, dl_, K_->adj_, n_, out4_),
+    amd::check(smg_gp_exp_quad_cov_tangent_rev(c, x_, n_, s_, l_, ds_, dl_, K_->adj(), n_, out4_),
                "gp_exp_quad_cov");
     for (int i = 0; i < 4; ++i)
       if (vis_[i]) add_pending_adjoint(vis_[i], out4_ + i);
@@ -49,10 +49,11 @@ class phi_dev_vari : public device_vari {
   dev_matrix_vari* Y_;
   explicit phi_dev_vari(dev_matrix_vari* X)
       : device_vari(0.0), X_(X), Y_(new dev_matrix_vari(X->rows_, X->cols_, dev_structure::lower)) {
+    X->want_adjoint();
     amd::check(smg_phi(amd::ctx(), X_->rows_, X_->val(), X_->rows_, Y_->raw_val(), Y_->rows_, 0), "phi");
   }
   void chain() override {
-    amd::check(smg_phi(amd::ctx(), X_->rows_, Y_->adj_, Y_->rows_, X_->adj_, X_->rows_, 1), "phi");
+    amd::check(smg_phi(amd::ctx(), X_->rows_, Y_->adj(), Y_->rows_, X_->adj(), X_->rows_, 1), "phi");
   }
 };
 
@@ -60,12 +61,15 @@ class dot_dev_vari : public device_vari {
  public:
   dev_matrix_vari* x_;
   dev_matrix_vari* y_;
-  dot_dev_vari(double v, dev_matrix_vari* x, dev_matrix_vari* y) : device_vari(v), x_(x), y_(y) {}
+  dot_dev_vari(double v, dev_matrix_vari* x, dev_matrix_vari* y) : device_vari(v), x_(x), y_(y) {
+    x->want_adjoint();
+    y->want_adjoint();
+  }
   void chain() override {
     smg_ctx* c = amd::ctx();
     const long long n = (long long)x_->size();
-    amd::check(smg_axpy(c, n, adj_, y_->val(), 1, x_->adj_, 1), "dot_product");
-    amd::check(smg_axpy(c, n, adj_, x_->val(), 1, y_->adj_, 1), "dot_product");
+    amd::check(smg_axpy(c, n, adj_, y_->val(), 1, x_->adj(), 1), "dot_product");
+    amd::check(smg_axpy(c, n, adj_, x_->val(), 1, y_->adj(), 1), "dot_product");
   }
 };
 
@@ -73,10 +77,13 @@ class diag_ratio_dev_vari : public device_vari {
  public:
   dev_matrix_vari* A_;
   dev_matrix_vari* B_;
-  diag_ratio_dev_vari(double v, dev_matrix_vari* A, dev_matrix_vari* B) : device_vari(v), A_(A), B_(B) {}
+  diag_ratio_dev_vari(double v, dev_matrix_vari* A, dev_matrix_vari* B) : device_vari(v), A_(A), B_(B) {
+    A->want_adjoint();
+    B->want_adjoint();
+  }
   void chain() override {
     amd::check(smg_diag_ratio_rev(amd::ctx(), A_->rows_, A_->val(), A_->rows_, B_->val(), B_->rows_,
-                                  adj_, A_->adj_, A_->rows_, B_->adj_, B_->rows_),
+                                  adj_, A_->adj(), A_->rows_, B_->adj(), B_->rows_),
                "diag_ratio_sum");
   }
 };

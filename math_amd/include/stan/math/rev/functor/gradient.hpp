@@ -71,7 +71,7 @@ void gradient(const F& f, const dev_data<double>& x, double& fx, double* grad_de
     var fx_var = f(dev_var_matrix(leaf));
     fx = fx_var.val();
     grad(fx_var.vi_);
-    amd::check(smg_memcpy_d2d(c, grad_dev, leaf->adj_, n * sizeof(double)), "gradient");
+    amd::check(smg_memcpy_d2d(c, grad_dev, leaf->adj(), n * sizeof(double)), "gradient");
   } catch (const std::exception& e) {
     recover_memory_nested();
     throw;

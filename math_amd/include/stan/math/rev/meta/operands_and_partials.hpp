@@ -283,7 +283,7 @@ class ops_partials_vari : public local_adjoint_vari {
     for (size_t i = 0; i < size_; ++i) varis_[i]->adj_ += adj_ * partials_[i];
     for (int i = 0; i < ndev_; ++i)
       amd::check(smg_axpy(amd::ctx(), (long long)dev_[i].op->size(), adj_, dev_[i].partials, 1,
-                          dev_[i].op->adj_, 1),
+                          dev_[i].op->adj(), 1),
                  "operands_and_partials");
   }
 };
