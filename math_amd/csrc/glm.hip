@@ -101,8 +101,9 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   const double inv_sigma = KIND == 1 ? 1.0 / ab[1 + M] : 0.0;
   const double phi = KIND == 3 ? ab[1 + M] : 0.0;
   const double log_phi = KIND == 3 ? log(phi) : 0.0;
-  // KIND 3 without columns (M == 0, x may be null): every x load reads the zero page
-  const bool nox = KIND == 3 && M == 0;
+  // no columns (M == 0, x may be null; the column clamp below would give -1):
+  // every x load reads the zero page, for every kind
+  const bool nox = M == 0;
   const double* __restrict__ xb = nox ? g_glm_zero : x;
   const long long ldc = nox ? 0 : ldx, rend = nox ? 1 : R;
   const long long ntiles = (R + RB - 1) / RB;

@@ -59,6 +59,34 @@ def near_rel(actual, expected, rtol, atol=None, what=""):
     return float(rel[~small].max()) if np.any(~small) else 0.0
 
 
+# --------------------------------------------------------------- reduced sums
+def worst(got, ref, scale):
+    """max |got - ref| / scale over the entries (0 where both vanish)."""
+    got, ref, scale = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (got, ref, scale))
+    assert np.all(np.isfinite(got)), got
+    diff = np.abs(got - ref)
+    return float(np.max(np.where(diff == 0.0, 0.0, diff / np.maximum(scale, 1e-300)))) if got.size else 0.0
+
+
+def check_sums(got, ref, what, b_sum=1e-12, b_phi=1e-11, b_rel=1e-10):
+    """`got` {name: value} against `ref` {name: (value, abs)}: every sum on the scale
+    of the sum of its terms' absolute values (within b_sum of it; phi' within
+    b_phi; alpha' and beta' also pass within b_rel of their own value where
+    that is looser); prints the worst ratio of each."""
+    for k, (want, scale) in ref.items():
+        if k not in got:
+            continue
+        r = worst(got[k], want, scale)
+        print(f"{what} {k}: |diff| / abs-term sum = {r:.3e}")
+        if k == "phi'":
+            assert r <= b_phi, (what, k, r)
+        elif k in ("alpha'", "beta'") and b_rel is not None:
+            g, w, sc = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (got[k], want, scale))
+            assert np.all(np.abs(g - w) <= np.maximum(b_sum * sc, b_rel * np.abs(w))), (what, k, r)
+        else:
+            assert r <= b_sum, (what, k, r)
+
+
 # --------------------------------------------------------------- prebuilt binaries
 def prebuilt(path):
     """path, after checking that the binary was built from the tree's sources

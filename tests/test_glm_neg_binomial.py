@@ -43,7 +43,7 @@ import pytest
 from scipy.special import digamma, gammaln
 
 import gen
-from _util import ROOT, near_rel, prebuilt
+from _util import ROOT, check_sums, near_rel, prebuilt
 
 gpu = pytest.mark.gpu
 
@@ -159,31 +159,6 @@ def nb_mp(y, x, alpha, beta, phi):
         res = {k: (float(v[0]), float(v[1])) for k, v in out.items()}
         res["beta'"] = (np.array([float(v) for v in bsum]), np.array([float(v) for v in babs]))
         return res
-
-
-def worst(got, ref, scale):
-    """max |got - ref| / scale over the entries (0 where both vanish)."""
-    got, ref, scale = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (got, ref, scale))
-    assert np.all(np.isfinite(got)), got
-    diff = np.abs(got - ref)
-    return float(np.max(np.where(diff == 0.0, 0.0, diff / np.maximum(scale, 1e-300)))) if got.size else 0.0
-
-
-def check_sums(got, ref, what, b_sum=1e-12, b_phi=1e-11, b_rel=1e-10):
-    """`got` {name: value} against `ref` {name: (value, abs)}: the bounds of the
-    module docstring; prints the worst ratio of each."""
-    for k, (want, scale) in ref.items():
-        if k not in got:
-            continue
-        r = worst(got[k], want, scale)
-        print(f"{what} {k}: |diff| / abs-term sum = {r:.3e}")
-        if k == "phi'":
-            assert r <= b_phi, (what, k, r)
-        elif k in ("alpha'", "beta'") and b_rel is not None:
-            g, w, sc = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (got[k], want, scale))
-            assert np.all(np.abs(g - w) <= np.maximum(b_sum * sc, b_rel * np.abs(w))), (what, k, r)
-        else:
-            assert r <= b_sum, (what, k, r)
 
 
 # ------------------------------------------------------------ 1. the yardstick (no GPU)
