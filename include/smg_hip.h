@@ -892,6 +892,31 @@ int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x,
                                long long R, int M, long long ldx,
                                const double* alpha_beta_phi, double* ws, double* out);
 
+/* ordered_logistic_glm_lpmf(y | x, beta, cuts): y in 1..C, cut-points
+ * c_1 < ... < c_{C-1} (c_0 = -inf, c_C = +inf), no intercept, ONE fused pass
+ * over x:
+ *   beta_cuts = [beta(M), cuts(C - 1)] (device);
+ *   out (M + C doubles) = [logp, x^T theta' (M), cuts' (C - 1)] with
+ *   eta = x beta, k = y, a = c_k - eta, b = c_{k-1} - eta,
+ *   logp = sum log(logistic(a) - logistic(b)),
+ *   theta' = [k > 1] logistic(b) - [k < C] logistic(-a),
+ *   cuts'_j = sum_{y = j} (logistic(-a) + r_j) - sum_{y = j+1} (logistic(b) + r_{j+1}),
+ *   r_k = 1 / expm1(c_k - c_{k-1}) (0 for k = 1 and k = C).
+ * Every term is evaluated from exp(-|a|), exp(-|b|) and the cut-point gaps,
+ * so logp is finite for finite eta of any size and for gaps down to one ulp.
+ * The cut-point sums are binned per class in fixed row order without
+ * atomics: the same inputs give the same bits.
+ * M <= 256 and C <= 16, else SMG_ERR_ARG.  M == 0: x may be null, eta = 0.
+ * C == 1: logp and every partial are 0.  R == 0 writes zeros.
+ * ws: >= smg_ordered_logistic_glm_ws_doubles(R, M, C).  y in 1..C, the order
+ * and finiteness of the cut-points are checked by the caller
+ * (smg_check_bounded_int); a y outside 1..C is clamped for the cut-point
+ * lookup (no out-of-range access), and that row's result is unspecified. */
+long long smg_ordered_logistic_glm_ws_doubles(long long R, int M, int C);
+int smg_ordered_logistic_glm(smg_ctx* ctx, const int* y, const double* x,
+                             long long R, int M, long long ldx, int C,
+                             const double* beta_cuts, double* ws, double* out);
+
 /* categorical_logit_glm_lpmf<false>(y | x, alpha, beta)
  * (prim/mat/prob/categorical_logit_glm_lpmf.hpp:38-146): x R x M
  * (column-major, ld ldx), alpha_beta = [alpha(C), beta(M x C column-major)],

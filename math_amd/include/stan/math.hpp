@@ -29,6 +29,7 @@
 #include <stan/math/rev/fun/poisson_log_glm_lpmf.hpp>
 #include <stan/math/rev/fun/neg_binomial_2_log_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/ordered_logistic_glm_lpmf.hpp>
 #include <stan/math/rev/fun/spd_functors.hpp>
 #include <stan/math/rev/fun/log_determinant.hpp>
 #include <stan/math/rev/functor/gradient.hpp>

@@ -45,6 +45,7 @@
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
 #include <stan/math/rev/fun/neg_binomial_2_log_glm_lpmf.hpp>
+#include <stan/math/rev/fun/ordered_logistic_glm_lpmf.hpp>
 #include <stan/math/rev/fun/spd_functors.hpp>
 #include <stan/math/rev/fun/lgamma.hpp>
 #include <stan/math/rev/fun/log_sum_exp.hpp>
@@ -553,6 +554,20 @@ inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const matrix_
     internal::glm_size_mismatch("neg_binomial_2_log_glm_lpmf", "Vector of dependent variables",
                                 (long long)y.size(), x.rows());
   return neg_binomial_2_log_glm_lpmf<propto>(y, xv, int(x.cols()), alpha, b, phi);
+}
+
+/** ordered_logistic_glm_lpmf(y, x, beta, cuts) with Eigen x / beta / cuts;
+ * beta and cuts each var or double (both double: a double). */
+template <bool propto = false, typename T_b, int RB, typename T_c, int RC>
+inline auto ordered_logistic_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
+                                      const Eigen::Matrix<T_b, RB, 1>& beta, const Eigen::Matrix<T_c, RC, 1>& cuts) {
+  std::vector<T_b> b(beta.data(), beta.data() + beta.size());
+  std::vector<T_c> c(cuts.data(), cuts.data() + cuts.size());
+  std::vector<double> xv(x.data(), x.data() + x.size());
+  if (y.size() != size_t(x.rows()))
+    internal::glm_size_mismatch("ordered_logistic_glm_lpmf", "Vector of dependent variables", (long long)y.size(),
+                                x.rows());
+  return ordered_logistic_glm_lpmf<propto>(y, xv, int(x.cols()), b, c);
 }
 
 namespace internal {
