@@ -892,6 +892,35 @@ int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x,
                                long long R, int M, long long ldx,
                                const double* alpha_beta_phi, double* ws, double* out);
 
+/* The four GLMs above with one intercept per row (the reference's vector
+ * alpha: exposure offsets, random effects, a latent GP mean), the same ONE
+ * fused pass over x:
+ *   kind 0 bernoulli_logit, 1 normal_id, 2 poisson_log, 3 neg_binomial_2_log;
+ *   y: int* (kind 1: double*);  theta_i = x_i beta + alpha_vec[i];
+ *   alpha_vec: R doubles (device);
+ *   ab: as the kind's scalar entry lays it out ([alpha, beta(M)], kind 1
+ *   [alpha, beta(M), sigma], kind 3 [alpha, beta(M), phi]); slot 0 is ignored;
+ *   out: as the kind's scalar entry, slot 1 = sum theta':
+ *     kind 0 (M + 3): [logp, sum theta', x^T theta' (M), number of y outside {0, 1}]
+ *            (the layout of smg_bernoulli_logit_glm_checked),
+ *     kind 1 (M + 2): [sum y_scaled^2, sum mu', x^T mu' (M)],
+ *     kind 2 (M + 3): [sum(y theta - exp theta), sum theta', x^T theta' (M), sum lgamma(y + 1)],
+ *     kind 3 (M + 6): [A, sum theta', x^T theta' (M), B, C, D, phi'];
+ *   theta_adj: null, or R doubles that receive the rows' theta' -- the partial
+ *   of each row's intercept (kind 1: mu' = y_scaled / sigma, kind 3:
+ *   y - (y + phi) s); written, not accumulated; nothing beyond row R - 1.
+ * Deterministic: a constant alpha_vec gives the scalar entry's bits.
+ * ws: >= smg_glm_ws_doubles(R, M) (kind 3: smg_neg_binomial_2_log_glm_ws_doubles).
+ * M == 0: x may be null.  R == 0 writes zeros.  Kind 0 takes M > 256 by the
+ * generic path (GEMM, row pass, GEMM; R < 2^31); kinds 1-3 need M <= 256.
+ * SMG_ERR_ARG: kind outside 0..3, a null alpha_vec with R > 0, M > 256 for
+ * kinds 1-3, and the scalar entries' argument errors.  The y domain (kinds 2,
+ * 3), sigma > 0 and phi > 0 are checked by the caller. */
+int smg_glm_vec_intercept(smg_ctx* ctx, int kind, const void* y, const double* x,
+                          long long R, int M, long long ldx,
+                          const double* alpha_vec, const double* ab,
+                          double* ws, double* out, double* theta_adj);
+
 /* ordered_logistic_glm_lpmf(y | x, beta, cuts): y in 1..C, cut-points
  * c_1 < ... < c_{C-1} (c_0 = -inf, c_C = +inf), no intercept, ONE fused pass
  * over x:

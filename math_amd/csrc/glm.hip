@@ -1,4 +1,5 @@
-// The GLM reducers over rows, each in ONE pass over x (scalar intercept):
+// The GLM reducers over rows, each in ONE pass over x (KIND 0-3: scalar
+// intercept, or one intercept per row -- AV below):
 //   KIND 0  bernoulli_logit_glm_lpmf  (y int in {0,1})
 //   KIND 1  normal_id_glm_lpdf        (y double, scalar sigma)
 //   KIND 2  poisson_log_glm_lpmf      (y int >= 0)
@@ -118,10 +119,18 @@ __device__ double g_glm_zero[2] = {0.0, 0.0};
 // into partial slot M + 2 -- the pass reads y anyway, so the check costs no
 // extra launch and no extra pass over y.
 // KIND 4 takes its number of classes C in the check_y argument.
-template <int KIND, int RB, int NT, bool NTL>
+// AV (KIND 0-3): one intercept per row, av[R], in place of ab[0] (not read);
+// the row's value is loaded with its y and carried with it, and the row's
+// theta' -- the partial of its intercept -- is stored to thp[R] unless thp is
+// null.  Everything of this mode sits under `if (AV)`: the scalar
+// instantiations are the code they were.
+template <int KIND, int RB, int NT, bool NTL, bool AV = false>
 __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const double* __restrict__ x, long long R,
                                              int M, long long ldx, const double* __restrict__ ab,
-                                             double* __restrict__ part, int check_y) {
+                                             double* __restrict__ part, int check_y,
+                                             const double* __restrict__ av = nullptr,
+                                             double* __restrict__ thp = nullptr) {
+  static_assert(!AV || KIND < 4, "KIND 4 has no intercept");
   constexpr int G = NT / RB, Q = MMAX / G;
   const int* __restrict__ y = static_cast<const int*>(yv);
   const double* __restrict__ yd = static_cast<const double*>(yv);
@@ -136,7 +145,7 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   __shared__ double ol_bin[OLC][OLW];
   const int t = threadIdx.x, r = t % RB, g = t / RB;
   for (int c = t; c < MMAX; c += NT) beta[c] = c < M ? ab[(KIND == 4 ? 0 : 1) + c] : 0.0;
-  const double alpha = KIND == 4 ? 0.0 : ab[0];
+  const double alpha = (KIND == 4 || AV) ? 0.0 : ab[0];
   const int C = KIND == 4 ? (check_y < 1 ? 1 : (check_y > OL_CMAX ? OL_CMAX : check_y)) : 0;
   if (KIND == 4) {
     if (t <= C) {  // class t's constants (t = 0: only c_0)
@@ -167,15 +176,18 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   double b_acc = 0.0, d_acc = 0.0, f_acc = 0.0;  // KIND 3: B, D and phi'
   double xc[Q], xn[Q];
   double yc = 0.0, yn = 0.0;  // the row's y (as double), loaded one tile ahead with x
+  double ac = 0.0, an = 0.0;  // AV: the row's intercept, loaded and carried with its y
   // Loads are straight-line code: addresses are clamped into x and the
   // values masked where they are consumed (a branch or a select next to a
   // load makes the compiler wait for it there), and y is issued before x so
-  // that waiting for it leaves the x loads in flight (vmcnt counts in order).
-  auto load = [&](double (&v)[Q], double& yv_, long long tile) {
+  // that waiting for it leaves the x loads in flight (vmcnt counts in order);
+  // so is the row's intercept (AV), at y's clamped row.
+  auto load = [&](double (&v)[Q], double& yv_, double& av_, long long tile) {
     const long long gr = tile * RB + r;
     const size_t ry = (size_t)(gr < R ? gr : R - 1);
     const size_t rc = (size_t)(gr < rend ? gr : rend - 1);
     yv_ = KIND == 1 ? yd[ry] : (double)y[ry];
+    if (AV) av_ = av[ry];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const int c = g + G * q;
@@ -187,8 +199,9 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   // one tile's work on the registers cur / cy (the other buffer's loads
   // stay in flight meanwhile); ping-pong buffers instead of a copy, which
   // would wait for the loads
-  auto work = [&](double (&cur)[Q], double cy, long long tile, int buf) {
+  auto work = [&](double (&cur)[Q], double cy, double ca, long long tile, int buf) {
     const long long gr = tile * RB + r;
+    const double al = AV ? ca : alpha;  // the row's intercept
 #pragma unroll
     for (int q = 0; q < Q; ++q) cur[q] = (gr < R && g + G * q < M) ? cur[q] : 0.0;
     double e = 0.0;
@@ -204,23 +217,23 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
       double lp;
       if (KIND == 0) {
         const double sgn = 2.0 * cy - 1.0;
-        const double yt = sgn * (eta + alpha);
+        const double yt = sgn * (eta + al);
         const double ex = exp(-yt);
         lp = yt > 20.0 ? -ex : (yt < -20.0 ? yt : -log1p(ex));
         th = yt > 20.0 ? -ex : (yt < -20.0 ? sgn : sgn * ex / (ex + 1));
       } else if (KIND == 1) {
-        const double ys = (cy - eta - alpha) * inv_sigma;
+        const double ys = (cy - eta - al) * inv_sigma;
         lp = ys * ys;
         th = ys * inv_sigma;
       } else if (KIND == 2) {
         const double yi = cy;
-        const double theta = eta + alpha;
+        const double theta = eta + al;
         const double ex = exp(theta);
         lp = yi * theta - ex;
         th = yi - ex;
       } else if (KIND == 3) {
         const double yi = cy;
-        const double theta = eta + alpha;
+        const double theta = eta + al;
         const double d = theta - log_phi;
         const double e = exp(-fabs(d));  // in [0, 1]: never exp(theta) itself
         const double lse = fmax(theta, log_phi) + log1p(e);
@@ -265,6 +278,13 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
         lp_acc += lp;
         ga_acc += th;
         if (KIND == 0) c_acc += (cy != 0.0 && cy != 1.0) ? 1.0 : 0.0;
+        // lanes 0-31 of wave 0: one 256-byte segment per tile, rows >= R never.
+        // Measured at 1e6 x 256: 1.06-1.09x the scalar kernel's time with the
+        // store, 1.00-1.06x without.  Stored one tile late instead (behind the
+        // next tile's loads, th and gr carried in registers): 1.07-1.10x, and
+        // 1.01-1.09x without the store -- not kept.
+        if (AV)
+          if (thp) thp[gr] = th;
       }
     }
 #pragma unroll
@@ -275,15 +295,15 @@ __device__ __forceinline__ void glm_reg_body(const void* __restrict__ yv, const 
   const long long gs = gridDim.x;
   auto clampt = [&](long long tt) { return tt < ntiles ? tt : tile; };
   {
-    if (tile < ntiles) load(xc, yc, tile);
+    if (tile < ntiles) load(xc, yc, ac, tile);
     for (;;) {
       if (tile >= ntiles) break;
-      load(xn, yn, clampt(tile + gs));
-      work(xc, yc, tile, 0);
+      load(xn, yn, an, clampt(tile + gs));
+      work(xc, yc, ac, tile, 0);
       tile += gs;
       if (tile >= ntiles) break;
-      load(xc, yc, clampt(tile + gs));
-      work(xn, yn, tile, 1);
+      load(xc, yc, ac, clampt(tile + gs));
+      work(xn, yn, an, tile, 1);
       tile += gs;
     }
   }
@@ -376,6 +396,17 @@ __global__ __launch_bounds__(NT) void k_glm_reg(const void* __restrict__ yv, con
   glm_reg_body<KIND, RB, NT, NTL>(yv, x, R, M, ldx, ab, part, check_y);
 }
 
+// the vector-intercept form (KIND 0-3): av[R] per-row intercepts, thp[R] the
+// rows' theta' (null: not stored); ab[0] is not read
+template <int KIND, int RB, int NT, bool NTL = false>
+__global__ __launch_bounds__(NT) void k_glm_reg_av(const void* __restrict__ yv, const double* __restrict__ x,
+                                                   long long R, int M, long long ldx,
+                                                   const double* __restrict__ ab, double* __restrict__ part,
+                                                   int check_y, const double* __restrict__ av,
+                                                   double* __restrict__ thp) {
+  glm_reg_body<KIND, RB, NT, NTL, true>(yv, x, R, M, ldx, ab, part, check_y, av, thp);
+}
+
 // [alpha, beta(M)] as a kernel argument: the launch carries the parameters,
 // no host-to-device copy ahead of it
 struct glm_ab_arg {
@@ -440,6 +471,15 @@ int glm_launch(hipStream_t st, const void* y, const double* x, long long R, int 
                const double* ab, double* ws, int check_y = 0) {
   const int nb = glm_blocks(R);
   hipLaunchKernelGGL((k_glm_reg<KIND, 32, 512, true>), dim3(nb), dim3(512), 0, st, y, x, R, M, ldx, ab, ws, check_y);
+  return nb;
+}
+
+template <int KIND>
+int glm_launch_av(hipStream_t st, const void* y, const double* x, long long R, int M, long long ldx,
+                  const double* ab, double* ws, int check_y, const double* av, double* thp) {
+  const int nb = glm_blocks(R);
+  hipLaunchKernelGGL((k_glm_reg_av<KIND, 32, 512, true>), dim3(nb), dim3(512), 0, st, y, x, R, M, ldx, ab, ws, check_y,
+                     av, thp);
   return nb;
 }
 
@@ -571,6 +611,34 @@ __global__ void k_glm_rows(const int* __restrict__ y, const double* __restrict__
     lp += yt > 20.0 ? -e : (yt < -20.0 ? yt : -log1p(e));
     const double d = yt > 20.0 ? -e : (yt < -20.0 ? sgn : sgn * e / (e + 1));
     th[i] = d;
+    ga += d;
+  }
+  lp = block_sum(lp, lds);
+  __syncthreads();
+  ga = block_sum(ga, lds);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = lp;
+    part[2 * blockIdx.x + 1] = ga;
+  }
+}
+
+// k_glm_rows with one intercept per row, av[R]; theta' also goes to thp[R]
+// unless it is null (th feeds the x^T theta' GEMM).  A kernel of its own:
+// k_glm_rows stays the code it was.
+__global__ void k_glm_rows_av(const int* __restrict__ y, const double* __restrict__ eta, long long R,
+                              const double* __restrict__ av, double* __restrict__ th, double* __restrict__ thp,
+                              double* part) {
+  __shared__ double lds[16];
+  double lp = 0.0, ga = 0.0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < R;
+       i += (long long)gridDim.x * blockDim.x) {
+    const double sgn = 2.0 * y[i] - 1.0;
+    const double yt = sgn * (eta[i] + av[i]);
+    const double e = exp(-yt);
+    lp += yt > 20.0 ? -e : (yt < -20.0 ? yt : -log1p(e));
+    const double d = yt > 20.0 ? -e : (yt < -20.0 ? sgn : sgn * e / (e + 1));
+    th[i] = d;
+    if (thp) thp[i] = d;
     ga += d;
   }
   lp = block_sum(lp, lds);
@@ -775,6 +843,49 @@ int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x, long
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<3>(ctx->stream, y, x, R, M, ldx, abp, ws);
   smg_reduce_partials(ctx, ws, nb, M + 6, out, 0);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// One intercept per row (kinds 0-3): the same fused pass with alpha_vec[R] in
+// place of ab[0]; theta_adj[R] (may be null) receives the rows' theta', the
+// partials of their intercepts.  `out` as the kind's scalar entry lays it out
+// (kind 0: the _checked form).
+int smg_glm_vec_intercept(smg_ctx* ctx, int kind, const void* y, const double* x, long long R, int M,
+                          long long ldx, const double* alpha_vec, const double* ab, double* ws, double* out,
+                          double* theta_adj) {
+  if (!ctx || kind < 0 || kind > 3 || R < 0 || M < 0 || !ab || !ws || !out) return SMG_ERR_ARG;
+  if (kind != 0 && M > MMAX) return SMG_ERR_ARG;
+  if (R > 0 && (!y || !alpha_vec || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  const int W = kind == 3 ? M + 6 : (kind == 1 ? M + 2 : M + 3);
+  if (R == 0) return smg_memset(ctx, out, 0, sizeof(double) * W);
+  if (M > MMAX) {  // kind 0's generic path: eta = x beta (GEMM n = 1), theta' per row, beta' = x^T theta'
+    if (R > INT_MAX) return SMG_ERR_ARG;  // GEMM dimensions
+    int rc = smg_memset(ctx, out + M + 2, 0, sizeof(double));
+    if (!rc) rc = smg_check_bounded_int(ctx, static_cast<const int*>(y), R, 0, 1, out + M + 2);
+    if (rc) return rc;
+    smg_prof_scope prof(ctx, SMG_FAM_GLM);
+    double* eta = ws;
+    double* th = ws + R;
+    double* part = ws + 2 * R;
+    rc = smg_gemm_impl(ctx, 0, 0, 0, (int)R, 1, M, 1.0, x, (int)ldx, ab + 1, M, 0.0, eta, (int)R);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_glm_rows_av, dim3(1024), dim3(256), 0, ctx->stream, static_cast<const int*>(y), eta, R,
+                       alpha_vec, th, theta_adj, part);
+    smg_reduce_partials(ctx, part, 1024, 2, out, 0);
+    rc = smg_gemm_impl(ctx, 1, 0, 0, M, 1, (int)R, 1.0, x, (int)ldx, th, (int)R, 0.0, out + 2, M);
+    SMG_LAUNCH_CHECK();
+    return rc;
+  }
+  smg_prof_scope prof(ctx, SMG_FAM_GLM);
+  int nb;
+  switch (kind) {
+    case 0: nb = glm_launch_av<0>(ctx->stream, y, x, R, M, ldx, ab, ws, 1, alpha_vec, theta_adj); break;
+    case 1: nb = glm_launch_av<1>(ctx->stream, y, x, R, M, ldx, ab, ws, 0, alpha_vec, theta_adj); break;
+    case 2: nb = glm_launch_av<2>(ctx->stream, y, x, R, M, ldx, ab, ws, 0, alpha_vec, theta_adj); break;
+    default: nb = glm_launch_av<3>(ctx->stream, y, x, R, M, ldx, ab, ws, 0, alpha_vec, theta_adj); break;
+  }
+  smg_reduce_partials(ctx, ws, nb, W, out, 0);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
 }

@@ -154,6 +154,8 @@ _SIGS = {
     "smg_poisson_log_glm": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P]),
     "smg_neg_binomial_2_log_glm_ws_doubles": (_L, [_L, _I]),
     "smg_neg_binomial_2_log_glm": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P]),
+    # (ctx, kind, y, x, R, M, ldx, alpha_vec, ab, ws, out, theta_adj)
+    "smg_glm_vec_intercept": (_I, [_P, _I, _P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
     "smg_ordered_logistic_glm_ws_doubles": (_L, [_L, _I, _I]),
     "smg_ordered_logistic_glm": (_I, [_P, _P, _P, _L, _I, _L, _I, _P, _P, _P]),
     "smg_glm_categorical_ws_doubles": (_L, [_L, _I, _I]),

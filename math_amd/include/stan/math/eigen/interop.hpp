@@ -556,6 +556,82 @@ inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const matrix_
   return neg_binomial_2_log_glm_lpmf<propto>(y, xv, int(x.cols()), alpha, b, phi);
 }
 
+namespace internal {
+/** An Eigen column or row vector of intercepts as the host vector the GLM
+ * overloads take (one intercept per row). */
+template <typename T, int RA, int CA>
+inline std::vector<T> glm_alpha_vector(const Eigen::Matrix<T, RA, CA>& a) {
+  static_assert(RA == 1 || CA == 1, "the vector of intercepts is a column or a row vector");
+  return std::vector<T>(a.data(), a.data() + a.size());
+}
+}  // namespace internal
+
+/** The Eigen signatures above with one intercept per row: alpha an Eigen column
+ * or row vector of double or var (all operands double: a double). */
+namespace internal {
+template <bool propto, typename T_a, int RA, int CA, typename T_b, int RB>
+inline auto bernoulli_glm_eigen_alpha(const std::vector<int>& y, const matrix_d& x,
+                                      const Eigen::Matrix<T_a, RA, CA>& alpha, const Eigen::Matrix<T_b, RB, 1>& beta) {
+  std::vector<T_b> b(beta.data(), beta.data() + beta.size());
+  std::vector<double> xv(x.data(), x.data() + x.size());
+  if (y.size() != size_t(x.rows()))
+    glm_size_mismatch("bernoulli_logit_glm_lpmf", "Vector of dependent variables", (long long)y.size(), x.rows());
+  return bernoulli_logit_glm_lpmf<propto>(y, xv, int(x.cols()), glm_alpha_vector(alpha), b);
+}
+}  // namespace internal
+template <bool propto = false, typename T_a, int RA, int CA, int RB>
+inline var bernoulli_logit_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
+                                    const Eigen::Matrix<T_a, RA, CA>& alpha, const Eigen::Matrix<var, RB, 1>& beta) {
+  return internal::bernoulli_glm_eigen_alpha<propto>(y, x, alpha, beta);
+}
+template <bool propto = false, typename T_a, int RA, int CA, int RB>
+inline auto bernoulli_logit_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
+                                     const Eigen::Matrix<T_a, RA, CA>& alpha,
+                                     const Eigen::Matrix<double, RB, 1>& beta) {
+  return internal::bernoulli_glm_eigen_alpha<propto>(y, x, alpha, beta);
+}
+template <bool propto = false, typename T_a, int RA, int CA, typename T_b, int RB, typename T_precision>
+inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
+                                        const Eigen::Matrix<T_a, RA, CA>& alpha, const Eigen::Matrix<T_b, RB, 1>& beta,
+                                        const T_precision& phi) {
+  return neg_binomial_2_log_glm_lpmf<propto>(y, x, internal::glm_alpha_vector(alpha), beta, phi);
+}
+/** poisson_log_glm_lpmf(y, x, alpha, beta) and normal_id_glm_lpdf(y, x, alpha,
+ * beta, sigma) with Eigen x / beta and alpha a scalar or an Eigen vector. */
+template <bool propto = false, typename T_alpha, typename T_b, int RB>
+inline auto poisson_log_glm_lpmf(const std::vector<int>& y, const matrix_d& x, const T_alpha& alpha,
+                                 const Eigen::Matrix<T_b, RB, 1>& beta) {
+  std::vector<T_b> b(beta.data(), beta.data() + beta.size());
+  std::vector<double> xv(x.data(), x.data() + x.size());
+  if (y.size() != size_t(x.rows()))
+    internal::glm_size_mismatch("poisson_log_glm_lpmf", "Vector of dependent variables", (long long)y.size(),
+                                x.rows());
+  return poisson_log_glm_lpmf<propto>(y, xv, int(x.cols()), alpha, b);
+}
+template <bool propto = false, typename T_a, int RA, int CA, typename T_b, int RB>
+inline auto poisson_log_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
+                                 const Eigen::Matrix<T_a, RA, CA>& alpha, const Eigen::Matrix<T_b, RB, 1>& beta) {
+  return poisson_log_glm_lpmf<propto>(y, x, internal::glm_alpha_vector(alpha), beta);
+}
+template <bool propto = false, int RY, typename T_alpha, typename T_b, int RB, typename T_scale>
+inline auto normal_id_glm_lpdf(const Eigen::Matrix<double, RY, 1>& y, const matrix_d& x, const T_alpha& alpha,
+                               const Eigen::Matrix<T_b, RB, 1>& beta, const T_scale& sigma) {
+  internal::normal_glm_check_scale(internal::glm_sigma_val(sigma));  // first, as the device form
+  std::vector<T_b> b(beta.data(), beta.data() + beta.size());
+  std::vector<double> yv(y.data(), y.data() + y.size());
+  std::vector<double> xv(x.data(), x.data() + x.size());
+  if (yv.size() != size_t(x.rows()))
+    internal::glm_size_mismatch("normal_id_glm_lpdf", "Vector of dependent variables", (long long)yv.size(),
+                                x.rows());
+  return normal_id_glm_lpdf<propto>(yv, xv, int(x.cols()), alpha, b, sigma);
+}
+template <bool propto = false, int RY, typename T_a, int RA, int CA, typename T_b, int RB, typename T_scale>
+inline auto normal_id_glm_lpdf(const Eigen::Matrix<double, RY, 1>& y, const matrix_d& x,
+                               const Eigen::Matrix<T_a, RA, CA>& alpha, const Eigen::Matrix<T_b, RB, 1>& beta,
+                               const T_scale& sigma) {
+  return normal_id_glm_lpdf<propto>(y, x, internal::glm_alpha_vector(alpha), beta, sigma);
+}
+
 /** ordered_logistic_glm_lpmf(y, x, beta, cuts) with Eigen x / beta / cuts;
  * beta and cuts each var or double (both double: a double). */
 template <bool propto = false, typename T_b, int RB, typename T_c, int RC>

@@ -34,7 +34,9 @@
 // Row shards with shard.distributed all-reduce the M + 6 sums and the y flag
 // in one call, and N is then the global row count; plain shards summed on the
 // tape each use their own rows (as normal_id_glm_lpdf does with N log sigma).
-// Not provided: vector alpha, vector phi, M > 256, the fvar<var> tangent.
+// alpha: a scalar, or one intercept per row (the vector forms of
+// bernoulli_logit_glm_lpmf.hpp).
+// Not provided: vector phi, M > 256, the fvar<var> tangent.
 
 #include <stan/math/rev/fun/normal_id_glm_lpdf.hpp>
 #include <stan/math/rev/fun/poisson_log_glm_lpmf.hpp>
@@ -77,6 +79,7 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
          "multidimensional values of the same shape.";
     throw std::invalid_argument(m.str());
   }
+  glm_check_alpha_size(fn, p, s.rows);
   smg_ctx* c = amd::ctx();
   // [alpha, beta(M), phi | out: A, alpha', beta'(M), B, C, D, phi' | flag]
   const size_t nbuf = size_t(2 * M + 9);
@@ -93,9 +96,12 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
   const bool any_var = p.any_var() || phi_vi;
   const bool phi_ok = phi > 0 && std::isfinite(phi);  // its error follows y's
   const bool run = phi_ok && s.total_rows > 0 && (any_var || !propto);
+  glm_vec_alpha va;  // one intercept per row: theta' is row-local, not reduced
   if (run && s.rows > 0) {
     double* ws = amd::alloc_doubles(size_t(smg_neg_binomial_2_log_glm_ws_doubles(s.rows, M)));
-    amd::check(smg_neg_binomial_2_log_glm(c, s.y, s.x, s.rows, M, s.ldx, abp, ws, out), fn);
+    va = glm_vec_alpha_prepare(p, s.rows);
+    amd::check(p.alpha_vec ? smg_glm_vec_intercept(c, 3, s.y, s.x, s.rows, M, s.ldx, va.av, abp, ws, out, va.thp)
+                           : smg_neg_binomial_2_log_glm(c, s.y, s.x, s.rows, M, s.ldx, abp, ws, out), fn);
   }
   // the M + 6 sums and the y flag are contiguous (zeros when not run): one
   // all-reduce carries them, so every rank throws together
@@ -119,6 +125,7 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
       m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
       throw std::domain_error(m.str());
     }
+    glm_throw_nonfinite_alpha_vec(fn, p, va);
     throw std::domain_error(std::string(fn) +
                             ": Matrix of independent variables is not finite, but must be finite!");
   }
@@ -132,6 +139,7 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
   double* g = ChainableStack::instance_->memalloc_.alloc_array<double>(size_t(M + 2));
   for (int j = 0; j <= M; ++j) g[j] = o[1 + j];
   g[M + 1] = o[M + 5];
+  if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, phi_vi, g, out + 2, M)};
   return glm_result{lp, new glm_sigma_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, phi_vi, g, out + 2, M)};
 }
 

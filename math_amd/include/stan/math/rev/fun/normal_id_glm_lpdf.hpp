@@ -109,6 +109,7 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
          "multidimensional values of the same shape.";
     throw std::invalid_argument(m.str());
   }
+  glm_check_alpha_size(fn, p, s.rows);
   const bool any_var = p.any_var() || sigma_vi;
   if (s.total_rows == 0 || (propto && !any_var)) return glm_result{};
   smg_ctx* c = amd::ctx();
@@ -121,9 +122,12 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
   for (int j = 0; j < M; ++j) h[1 + j] = p.beta[j];
   h[M + 1] = sigma;
   amd::to_device(buf, h.data(), h.size());
+  glm_vec_alpha va;  // one intercept per row: mu' is row-local, not reduced
   if (s.rows > 0) {
     double* ws = amd::alloc_doubles(size_t(smg_glm_ws_doubles(s.rows, M)));
-    amd::check(smg_normal_id_glm(c, s.yd, s.x, s.rows, M, s.ldx, abs, ws, out), fn);
+    va = glm_vec_alpha_prepare(p, s.rows);
+    amd::check(p.alpha_vec ? smg_glm_vec_intercept(c, 1, s.yd, s.x, s.rows, M, s.ldx, va.av, abs, ws, out, va.thp)
+                           : smg_normal_id_glm(c, s.yd, s.x, s.rows, M, s.ldx, abs, ws, out), fn);
   } else {
     amd::zero(out, size_t(M + 2));
   }
@@ -143,6 +147,7 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
       m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
       throw std::domain_error(m.str());
     }
+    glm_throw_nonfinite_alpha_vec(fn, p, va);
     std::ostringstream m;
     m << fn << ": Matrix of independent variables is " << sq << ", but must be finite!";
     throw std::domain_error(m.str());
@@ -156,6 +161,7 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
   double* g = ChainableStack::instance_->memalloc_.alloc_array<double>(size_t(M + 2));
   for (int j = 0; j <= M; ++j) g[j] = h[M + 3 + j];
   g[M + 1] = (sq - N) / sigma;
+  if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, sigma_vi, g, out + 2, M)};
   return glm_result{lp, new glm_sigma_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, sigma_vi, g,
                                                out + 2, M)};
 }

@@ -1,7 +1,9 @@
 #ifndef STAN_MATH_REV_FUN_POISSON_LOG_GLM_LPMF_HPP
 #define STAN_MATH_REV_FUN_POISSON_LOG_GLM_LPMF_HPP
 
-// poisson_log_glm_lpmf<propto>(y | x, alpha, beta), scalar intercept
+// poisson_log_glm_lpmf<propto>(y | x, alpha, beta), scalar intercept or one per
+// row (the vector forms of bernoulli_logit_glm_lpmf.hpp: exposure offsets,
+// random effects, a latent GP mean on the device)
 // (prim/mat/prob/poisson_log_glm_lpmf.hpp:37-123), with y and x resident on
 // the device: ONE fused pass over x (smg_poisson_log_glm) yields
 // [sum(y theta - exp theta), sum theta', x^T theta', sum lgamma(y + 1)],
@@ -70,6 +72,7 @@ inline glm_result poisson_glm_eval(const glm_shard& s, const glm_params& p) {
          "multidimensional values of the same shape.";
     throw std::invalid_argument(m.str());
   }
+  glm_check_alpha_size(fn, p, s.rows);
   smg_ctx* c = amd::ctx();
   // [alpha, beta(M) | out: s, alpha', beta'(M), lgamma sum | flag]
   double* buf = amd::alloc_doubles(size_t(2 * M + 5));
@@ -82,10 +85,13 @@ inline glm_result poisson_glm_eval(const glm_shard& s, const glm_params& p) {
   amd::to_device(buf, h.data(), h.size());
   amd::check(smg_check_bounded_int(c, s.y, s.rows, 0, INT_MAX, flag), fn);  // check_nonnegative (:61)
   const bool run = s.total_rows > 0 && (p.any_var() || !propto);
+  glm_vec_alpha va;  // one intercept per row: theta' is row-local, not reduced
   if (run) {
     if (s.rows > 0) {
       double* ws = amd::alloc_doubles(size_t(smg_glm_ws_doubles(s.rows, M)));
-      amd::check(smg_poisson_log_glm(c, s.y, s.x, s.rows, M, s.ldx, ab, ws, out), fn);
+      va = glm_vec_alpha_prepare(p, s.rows);
+      amd::check(p.alpha_vec ? smg_glm_vec_intercept(c, 2, s.y, s.x, s.rows, M, s.ldx, va.av, ab, ws, out, va.thp)
+                             : smg_poisson_log_glm(c, s.y, s.x, s.rows, M, s.ldx, ab, ws, out), fn);
     }
   }
   // [s, alpha', beta'(M), lgamma sum | flag] are contiguous (zeros when not
@@ -107,13 +113,15 @@ inline glm_result poisson_glm_eval(const glm_shard& s, const glm_params& p) {
       m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
       throw std::domain_error(m.str());
     }
+    glm_throw_nonfinite_alpha_vec(fn, p, va);
     throw std::domain_error(std::string(fn) +
                             ": Matrix of independent variables is not finite, but must be finite!");
   }
   const double lp = propto ? 0.0 : h[M + 1] - h[2 * M + 3];
   if (!p.any_var()) return glm_result{lp, nullptr};
-  double* g = ChainableStack::instance_->memalloc_.alloc_array<double>(size_t(M + 1));
+  double* g = ChainableStack::instance_->memalloc_.alloc_array<double>(size_t(M + 2));
   for (int j = 0; j <= M; ++j) g[j] = h[M + 2 + j];
+  if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, nullptr, g, out + 2, M)};
   return glm_result{lp, new glm_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, g, out + 2, M)};
 }
 
