@@ -56,11 +56,14 @@ __device__ double dev_digamma_1_2(double x) {
 __device__ double dev_digamma(double x) {
   double result = 0;
   if (x <= -1) {
+    // pi cot(pi (1 - x)) = -pi cot(pi r) with r = x - round(x) taken from x
+    // itself (exact): 1 - x is rounded where it crosses a binade, and the
+    // reference, which reduces after that, is off by |1 - x| 2^-53 pi^2 /
+    // sin^2(pi x) near the poles
+    const double r = x - round(x);
+    if (r == 0) return __longlong_as_double(0x7ff8000000000000LL);
+    result = -M_PI / tan(M_PI * r);
     x = 1 - x;
-    double rem = x - floor(x);
-    if (rem > 0.5) rem -= 1;
-    if (rem == 0) return __longlong_as_double(0x7ff8000000000000LL);
-    result = M_PI / tan(M_PI * rem);
   }
   if (x == 0) return __longlong_as_double(0x7ff8000000000000LL);
   if (isnan(x)) return x;
