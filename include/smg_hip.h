@@ -823,6 +823,34 @@ int smg_normal_lpdf_fused(smg_ctx* ctx, const double* y, const double* mu, const
                           double mu0, double sigma0, long long n, int include, double* res, double* gy,
                           double* gmu, double* gsigma);
 
+/* student_t_lpdf<propto>(y | nu, mu, sigma) (prim/scal/prob/student_t_lpdf.hpp)
+ * in smg_normal_lpdf_fused's form: checks, value and partials in ONE launch
+ * that completes before returning; a vector operand is a pointer (device
+ * memory or pinned host memory from smg_pinned_io), a NULL pointer selects the
+ * scalar y0 / nu0 / mu0 / sigma0.  With z = (y - mu)/sigma, q = z^2/nu,
+ * h = nu/2, include bits: 1 = -log sqrt(pi), 2 = -log sigma,
+ * 4 = -(h + 1/2) log1p(q), 8 = lgamma(h + 1/2) - lgamma(h) - 1/2 log nu
+ * (include_summand<propto, ...>).
+ * res (9) = [lp, bad_y, bad_nu, bad_mu, bad_sigma, y', nu', mu', sigma' (the
+ * reduced partials of scalar operands whose g pointer is non-null)].  bad_y:
+ * a NaN (check_not_nan); bad_mu: a non-finite element (check_finite); bad_nu
+ * and bad_sigma (check_positive_finite): bit 1 = an element failed > 0 (a NaN
+ * included), bit 2 = an element is +infinity.  Vector partials are WRITTEN
+ * (not accumulated).  n == 0 writes nine zeros.  Bitwise repeatable.
+ * Replaces the body of prim/scal/prob/student_t_lpdf.hpp. */
+int smg_student_t_lpdf_fused(smg_ctx* ctx, const double* y, const double* nu, const double* mu, const double* sigma,
+                             double y0, double nu0, double mu0, double sigma0, long long n, int include,
+                             double* res, double* gy, double* gnu, double* gmu, double* gsigma);
+/* cauchy_lpdf<propto>(y | mu, sigma) (prim/scal/prob/cauchy_lpdf.hpp), the
+ * same kernel's second specialisation, evaluated through z (finite at
+ * |z| = 1e150): include bits 1 = -log pi, 2 = -log sigma, 4 = -log1p(z^2);
+ * y' = -2z / (sigma (1 + z^2)), mu' = -y', sigma' = (z^2 - 1) / (sigma (1 + z^2)).
+ * res (9) in smg_student_t_lpdf_fused's layout, the nu columns 0.
+ * Replaces the body of prim/scal/prob/cauchy_lpdf.hpp. */
+int smg_cauchy_lpdf_fused(smg_ctx* ctx, const double* y, const double* mu, const double* sigma, double y0,
+                          double mu0, double sigma0, long long n, int include, double* res, double* gy,
+                          double* gmu, double* gsigma);
+
 /* bernoulli_logit_glm_lpmf<false>(y | x, alpha, beta), scalar alpha
  * (prim/mat/prob/bernoulli_logit_glm_lpmf.hpp:46-138) in ONE fused pass over
  * x (R x M column-major, leading dimension ldx):

@@ -148,6 +148,8 @@ _SIGS = {
     "smg_trigamma_fwd": (_I, [_P, _P, _L, _P]),
     "smg_normal_lpdf": (_I, [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P]),
     "smg_normal_lpdf_fused": (_I, [_P, _P, _P, _P, _D, _D, _D, _L, _I, _P, _P, _P, _P]),
+    "smg_student_t_lpdf_fused": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _L, _I, _P, _P, _P, _P, _P]),
+    "smg_cauchy_lpdf_fused": (_I, [_P, _P, _P, _P, _D, _D, _D, _L, _I, _P, _P, _P, _P]),
     "smg_glm_ws_doubles": (_L, [_L, _I]),
     "smg_bernoulli_logit_glm": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P]),
     "smg_normal_id_glm": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P]),
