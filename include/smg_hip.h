@@ -801,6 +801,60 @@ int smg_digamma_fwd(smg_ctx* ctx, const double* x, long long n, double* y);
 int smg_digamma_rev(smg_ctx* ctx, const double* x, long long n, const double* yadj, double* xadj);
 int smg_trigamma_fwd(smg_ctx* ctx, const double* x, long long n, double* y);
 
+/* Element-wise maps over device vectors (math_amd/csrc/elt.hip): what sits
+ * between the producers of a device matrix of vars and the reducers that
+ * take one (rev/fun/elt_ops.hpp).  Streaming kernels; none waits for the host.
+ * n == 0 is SMG_OK without a launch; a null ctx, n < 0, an unknown op or a
+ * missing buffer is SMG_ERR_ARG.
+ *
+ * Unary (prim/scal/fun/{exp,log,sqrt,square,inv,inv_logit,log_inv_logit,
+ * log1p_exp,tanh}.hpp; out-of-domain input gives the function's NaN / inf):
+ *   fwd: y[i] = f(x[i])
+ *   rev: xadj[i] += yadj[i] f'(x[i]), f' evaluated from x without
+ *        cancellation (y, the forward's output, is read by exp, sqrt and inv
+ *        only and may be null for the others). */
+enum smg_elt_unary {
+  SMG_ELT_EXP = 0,
+  SMG_ELT_LOG = 1,
+  SMG_ELT_SQRT = 2,
+  SMG_ELT_SQUARE = 3,
+  SMG_ELT_INV = 4,
+  SMG_ELT_INV_LOGIT = 5,
+  SMG_ELT_LOG_INV_LOGIT = 6,
+  SMG_ELT_LOG1P_EXP = 7,
+  SMG_ELT_TANH = 8
+};
+int smg_elt_unary_fwd(smg_ctx* ctx, int op, const double* x, long long n, double* y);
+int smg_elt_unary_rev(smg_ctx* ctx, int op, const double* x, const double* y, long long n, const double* yadj,
+                      double* xadj);
+/* Binary: c[i] = a[i] op b[i]; a NULL operand pointer selects the scalar
+ * a0 / b0 for every element.
+ *   rev: aadj[i] += cadj[i] dc/da, badj[i] += cadj[i] dc/db where the pointer
+ *        is non-null and its operand a vector.  aadj == badj is legal (the
+ *        same node as both operands: both contributions are added); c and
+ *        cadj alias no operand.  want_scalar: bit 1 (a) / bit 2 (b) of a
+ *        SCALAR operand asks for sum_i cadj[i] dc_i/d(scalar), WRITTEN (not
+ *        accumulated) to red[0] / red[1] (device); a vector operand's bit is
+ *        ignored and its slot untouched.  The sum has a fixed order (block
+ *        partials, block-order final sum): bitwise repeatable. */
+enum smg_elt_binary { SMG_ELT_ADD = 0, SMG_ELT_SUBTRACT = 1, SMG_ELT_MULTIPLY = 2, SMG_ELT_DIVIDE = 3 };
+int smg_elt_binary_fwd(smg_ctx* ctx, int op, const double* a, const double* b, double a0, double b0, long long n,
+                       double* c);
+int smg_elt_binary_rev(smg_ctx* ctx, int op, const double* a, const double* b, double a0, double b0, long long n,
+                       const double* cadj, double* aadj, double* badj, int want_scalar, double* red);
+/* The launch constants (tests, tools): shape[0..6] = threads of a block and
+ * the grid cap of the maps, the elements a lane of the forward maps and of
+ * the unary reverse takes per trip when every buffer is 16-byte aligned (2:
+ * one 16-byte access; a call with a buffer that is not takes one 8-byte
+ * element), threads, elements per block and grid cap of the reducing
+ * reverse, and the elements per lane and trip of the binary reverse. */
+int smg_elt_launch_shape(smg_ctx* ctx, int* shape);
+/* Elements per lane and trip of the context's aligned calls (timing and test
+ * hook): 0 the defaults (16 bytes for the forward maps and the unary reverse,
+ * 8 bytes for the binary reverse), 1 or 2 for every kernel.  Returns the
+ * previous value; any other argument only reads. */
+int smg_elt_set_width(smg_ctx* ctx, int elements);
+
 /* normal_lpdf<propto>(y | mu, sigma) (prim/scal/prob/normal_lpdf.hpp:36-119):
  * each operand is a device vector (stride 1) or scalar (stride 0) of n
  * broadcast elements.  include bits: 1 = NEG_LOG_SQRT_TWO_PI term,

@@ -274,6 +274,7 @@ int smg_ctx_create(int device, size_t initial, smg_ctx** out) {
   ctx->inv_mode = 0;
   ctx->gemm_stage = 0;
   ctx->gemm_cut = SMG_GEMM_CUT_DEFAULT;
+  ctx->elt_width = 0;
   ctx->host_scratch_size = 1u << 20;
   if (hipHostMalloc(&ctx->host_scratch, ctx->host_scratch_size, hipHostMallocDefault) != hipSuccess) {
     delete ctx;

@@ -97,6 +97,7 @@ struct smg_ctx {
   int inv_per_cu, inv_cus;  // k_inv_block512's occupancy per CU and the CUs (-1: not yet queried)
   int inv_mode;      // 1: the block inverses by the six-launch chain (smg_set_inv_block_mode, a test hook)
   int gemm_stage;    // the 64 x 64 GEMM tile's staging: 0 policy, 1 registers, 2 LDS-DMA where eligible (smg_set_gemm_stage_mode)
+  int elt_width;     // the element-wise maps' elements per lane and trip: 0 their defaults, 1 or 2 forced (smg_elt_set_width)
   int gemm_cut;      // the GEMMs' offset triangular K cuts: 1 applied, 0 ignored, 2 applied in the uncut tile placement (smg_set_gemm_cut_mode)
   // pinned host scratch
   void* host_scratch;

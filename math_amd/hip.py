@@ -146,6 +146,14 @@ _SIGS = {
     "smg_digamma_fwd": (_I, [_P, _P, _L, _P]),
     "smg_digamma_rev": (_I, [_P, _P, _L, _P, _P]),
     "smg_trigamma_fwd": (_I, [_P, _P, _L, _P]),
+    # element-wise maps: (ctx, op, x, n, y), (ctx, op, x, y, n, yadj, xadj),
+    # (ctx, op, a, b, a0, b0, n, c), (ctx, op, a, b, a0, b0, n, cadj, aadj, badj, want_scalar, red)
+    "smg_elt_unary_fwd": (_I, [_P, _I, _P, _L, _P]),
+    "smg_elt_unary_rev": (_I, [_P, _I, _P, _P, _L, _P, _P]),
+    "smg_elt_binary_fwd": (_I, [_P, _I, _P, _P, _D, _D, _L, _P]),
+    "smg_elt_binary_rev": (_I, [_P, _I, _P, _P, _D, _D, _L, _P, _P, _P, _I, _P]),
+    "smg_elt_launch_shape": (_I, [_P, ctypes.POINTER(_I)]),
+    "smg_elt_set_width": (_I, [_P, _I]),
     "smg_normal_lpdf": (_I, [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P]),
     "smg_normal_lpdf_fused": (_I, [_P, _P, _P, _P, _D, _D, _D, _L, _I, _P, _P, _P, _P]),
     "smg_student_t_lpdf_fused": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _L, _I, _P, _P, _P, _P, _P]),
