@@ -92,6 +92,7 @@
 // the compiler wait for the loads within the tile that issued them.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "smg_internal.h"
 #include "special_dev.h"  // dev_lgamma, dev_digamma (KIND 3)
@@ -599,46 +600,31 @@ int glm_cat_blocks(long long R) {
 }
 
 // ------------------------------------------------ generic path (M > 256)
-__global__ void k_glm_rows(const int* __restrict__ y, const double* __restrict__ eta, long long R,
-                           double alpha, double* __restrict__ th, double* part) {
-  __shared__ double lds[16];
-  double lp = 0.0, ga = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < R;
-       i += (long long)gridDim.x * blockDim.x) {
-    const double sgn = 2.0 * y[i] - 1.0;
-    const double yt = sgn * (eta[i] + alpha);
-    const double e = exp(-yt);
-    lp += yt > 20.0 ? -e : (yt < -20.0 ? yt : -log1p(e));
-    const double d = yt > 20.0 ? -e : (yt < -20.0 ? sgn : sgn * e / (e + 1));
-    th[i] = d;
-    ga += d;
-  }
-  lp = block_sum(lp, lds);
-  __syncthreads();
-  ga = block_sum(ga, lds);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = lp;
-    part[2 * blockIdx.x + 1] = ga;
-  }
-}
+// the intercept of row i: one scalar by value, or av[i], with theta' then also
+// stored to thp[i] unless thp is null (th feeds the x^T theta' GEMM)
+struct glm_rows_av {
+  const double* __restrict__ av;
+  double* __restrict__ thp;
+};
 
-// k_glm_rows with one intercept per row, av[R]; theta' also goes to thp[R]
-// unless it is null (th feeds the x^T theta' GEMM).  A kernel of its own:
-// k_glm_rows stays the code it was.
-__global__ void k_glm_rows_av(const int* __restrict__ y, const double* __restrict__ eta, long long R,
-                              const double* __restrict__ av, double* __restrict__ th, double* __restrict__ thp,
-                              double* part) {
+template <bool AV>
+__global__ void k_glm_rows(const int* __restrict__ y, const double* __restrict__ eta, long long R,
+                           std::conditional_t<AV, glm_rows_av, double> alpha, double* __restrict__ th, double* part) {
   __shared__ double lds[16];
   double lp = 0.0, ga = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < R;
        i += (long long)gridDim.x * blockDim.x) {
     const double sgn = 2.0 * y[i] - 1.0;
-    const double yt = sgn * (eta[i] + av[i]);
+    double a;
+    if constexpr (AV) a = alpha.av[i];
+    else a = alpha;
+    const double yt = sgn * (eta[i] + a);
     const double e = exp(-yt);
     lp += yt > 20.0 ? -e : (yt < -20.0 ? yt : -log1p(e));
     const double d = yt > 20.0 ? -e : (yt < -20.0 ? sgn : sgn * e / (e + 1));
     th[i] = d;
-    if (thp) thp[i] = d;
+    if constexpr (AV)
+      if (alpha.thp) alpha.thp[i] = d;
     ga += d;
   }
   lp = block_sum(lp, lds);
@@ -681,6 +667,38 @@ __global__ void k_glm_cat_rows(const int* __restrict__ y, double* __restrict__ l
   if (threadIdx.x == 0) part[blockIdx.x] = lp;
 }
 
+// bernoulli_logit at M > 256: eta = x beta (GEMM n = 1), theta' per row, beta'
+// = x^T theta'; out = [logp, alpha', beta'(M)].  av null: the scalar intercept
+// ab[0], fetched to the host between the GEMM and the row kernel.
+int glm_bernoulli_generic(smg_ctx* ctx, const int* y, const double* x, long long R, int M, long long ldx,
+                          const double* ab, const double* av, double* thp, double* ws, double* out) {
+  double* eta = ws;
+  double* th = ws + R;
+  double* part = ws + 2 * R;
+  int rc = smg_gemm_impl(ctx, 0, 0, 0, (int)R, 1, M, 1.0, x, (int)ldx, ab + 1, M, 0.0, eta, (int)R);
+  if (rc) return rc;
+  if (av) {
+    hipLaunchKernelGGL(k_glm_rows<true>, dim3(1024), dim3(256), 0, ctx->stream, y, eta, R, glm_rows_av{av, thp}, th,
+                       part);
+  } else {
+    double alpha_h;
+    rc = smg_memcpy_d2h(ctx, &alpha_h, ab, sizeof(double));
+    if (rc) return rc;
+    rc = smg_sync(ctx);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_glm_rows<false>, dim3(1024), dim3(256), 0, ctx->stream, y, eta, R, alpha_h, th, part);
+  }
+  smg_reduce_partials(ctx, part, 1024, 2, out, 0);
+  rc = smg_gemm_impl(ctx, 1, 0, 0, M, 1, (int)R, 1.0, x, (int)ldx, th, (int)R, 0.0, out + 2, M);
+  SMG_LAUNCH_CHECK();
+  return rc;
+}
+
+// every entry's data arguments: rows need y, columns need x with ldx >= R
+bool glm_bad_data(const void* y, const double* x, long long R, int M, long long ldx) {
+  return R > 0 && (!y || (M > 0 && (!x || ldx < R)));
+}
+
 }  // namespace
 
 extern "C" {
@@ -693,7 +711,7 @@ long long smg_glm_ws_doubles(long long R, int M) {
 int smg_bernoulli_logit_glm(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
                             long long ldx, const double* ab, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || !ab || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   if (M <= MMAX) {
     const int nb = glm_launch<0>(ctx->stream, y, x, R, M, ldx, ab, ws);
@@ -701,28 +719,13 @@ int smg_bernoulli_logit_glm(smg_ctx* ctx, const int* y, const double* x, long lo
     SMG_LAUNCH_CHECK();
     return SMG_OK;
   }
-  // eta = x beta (GEMM n = 1), theta' per row, beta' = x^T theta'
-  double* eta = ws;
-  double* th = ws + R;
-  double* part = ws + 2 * R;
-  int rc = smg_gemm_impl(ctx, 0, 0, 0, (int)R, 1, M, 1.0, x, (int)ldx, ab + 1, M, 0.0, eta, (int)R);
-  if (rc) return rc;
-  double alpha_h;
-  rc = smg_memcpy_d2h(ctx, &alpha_h, ab, sizeof(double));
-  if (rc) return rc;
-  rc = smg_sync(ctx);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_glm_rows, dim3(1024), dim3(256), 0, ctx->stream, y, eta, R, alpha_h, th, part);
-  smg_reduce_partials(ctx, part, 1024, 2, out, 0);
-  rc = smg_gemm_impl(ctx, 1, 0, 0, M, 1, (int)R, 1.0, x, (int)ldx, th, (int)R, 0.0, out + 2, M);
-  SMG_LAUNCH_CHECK();
-  return rc;
+  return glm_bernoulli_generic(ctx, y, x, R, M, ldx, ab, nullptr, nullptr, ws, out);
 }
 
 int smg_bernoulli_logit_glm_checked(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
                                     long long ldx, const double* ab, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || !ab || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   if (M > MMAX || R == 0) {  // the general path: a separate bound check
     int rc = smg_memset(ctx, out + M + 2, 0, sizeof(double));
     if (!rc) rc = smg_check_bounded_int(ctx, y, R, 0, 1, out + M + 2);
@@ -740,7 +743,7 @@ int smg_bernoulli_logit_glm_checked(smg_ctx* ctx, const int* y, const double* x,
 int smg_bernoulli_logit_glm_io(smg_ctx* ctx, const int* y, const double* x, long long R, int M, long long ldx,
                                double alpha, const double* beta, double* ws, double* out, double* out_h) {
   if (!ctx || R < 0 || M < 0 || !ws || !out || (M > 0 && !beta)) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   if (M > MMAX || R == 0) {  // the general path, then one copy back and a synchronisation
     double* ab = smg_ws(ctx, SMG_WS_GLM, (size_t)M + 1);
     double* h = (double*)smg_host_scratch(ctx, sizeof(double) * (M + 1));
@@ -780,7 +783,7 @@ int smg_categorical_logit_glm(smg_ctx* ctx, const int* y, const double* x, long 
                               long long ldx, int C, const double* alpha_beta, double* ws,
                               double* out) {
   if (!ctx || R < 0 || M < 0 || C < 1 || !alpha_beta || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   if (M <= MMAX && C <= CAT_CMAX) {
     const int nb = glm_cat_blocks(R);
@@ -812,7 +815,7 @@ int smg_categorical_logit_glm(smg_ctx* ctx, const int* y, const double* x, long 
 int smg_normal_id_glm(smg_ctx* ctx, const double* y, const double* x, long long R, int M,
                       long long ldx, const double* abs, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || M > MMAX || !abs || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<1>(ctx->stream, y, x, R, M, ldx, abs, ws);
   smg_reduce_partials(ctx, ws, nb, M + 2, out, 0);
@@ -823,7 +826,7 @@ int smg_normal_id_glm(smg_ctx* ctx, const double* y, const double* x, long long 
 int smg_poisson_log_glm(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
                         long long ldx, const double* ab, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || M > MMAX || !ab || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<2>(ctx->stream, y, x, R, M, ldx, ab, ws);
   smg_reduce_partials(ctx, ws, nb, M + 3, out, 0);
@@ -839,7 +842,7 @@ long long smg_neg_binomial_2_log_glm_ws_doubles(long long R, int M) {
 int smg_neg_binomial_2_log_glm(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
                                long long ldx, const double* abp, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || M > MMAX || !abp || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<3>(ctx->stream, y, x, R, M, ldx, abp, ws);
   smg_reduce_partials(ctx, ws, nb, M + 6, out, 0);
@@ -856,26 +859,16 @@ int smg_glm_vec_intercept(smg_ctx* ctx, int kind, const void* y, const double* x
                           double* theta_adj) {
   if (!ctx || kind < 0 || kind > 3 || R < 0 || M < 0 || !ab || !ws || !out) return SMG_ERR_ARG;
   if (kind != 0 && M > MMAX) return SMG_ERR_ARG;
-  if (R > 0 && (!y || !alpha_vec || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx) || (R > 0 && !alpha_vec)) return SMG_ERR_ARG;
   const int W = kind == 3 ? M + 6 : (kind == 1 ? M + 2 : M + 3);
   if (R == 0) return smg_memset(ctx, out, 0, sizeof(double) * W);
-  if (M > MMAX) {  // kind 0's generic path: eta = x beta (GEMM n = 1), theta' per row, beta' = x^T theta'
+  if (M > MMAX) {  // kind 0's generic path
     if (R > INT_MAX) return SMG_ERR_ARG;  // GEMM dimensions
     int rc = smg_memset(ctx, out + M + 2, 0, sizeof(double));
     if (!rc) rc = smg_check_bounded_int(ctx, static_cast<const int*>(y), R, 0, 1, out + M + 2);
     if (rc) return rc;
     smg_prof_scope prof(ctx, SMG_FAM_GLM);
-    double* eta = ws;
-    double* th = ws + R;
-    double* part = ws + 2 * R;
-    rc = smg_gemm_impl(ctx, 0, 0, 0, (int)R, 1, M, 1.0, x, (int)ldx, ab + 1, M, 0.0, eta, (int)R);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_glm_rows_av, dim3(1024), dim3(256), 0, ctx->stream, static_cast<const int*>(y), eta, R,
-                       alpha_vec, th, theta_adj, part);
-    smg_reduce_partials(ctx, part, 1024, 2, out, 0);
-    rc = smg_gemm_impl(ctx, 1, 0, 0, M, 1, (int)R, 1.0, x, (int)ldx, th, (int)R, 0.0, out + 2, M);
-    SMG_LAUNCH_CHECK();
-    return rc;
+    return glm_bernoulli_generic(ctx, static_cast<const int*>(y), x, R, M, ldx, ab, alpha_vec, theta_adj, ws, out);
   }
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   int nb;
@@ -898,7 +891,7 @@ long long smg_ordered_logistic_glm_ws_doubles(long long R, int M, int C) {
 int smg_ordered_logistic_glm(smg_ctx* ctx, const int* y, const double* x, long long R, int M,
                              long long ldx, int C, const double* bc, double* ws, double* out) {
   if (!ctx || R < 0 || M < 0 || M > MMAX || C < 1 || C > OL_CMAX || !bc || !ws || !out) return SMG_ERR_ARG;
-  if (R > 0 && (!y || (M > 0 && (!x || ldx < R)))) return SMG_ERR_ARG;
+  if (glm_bad_data(y, x, R, M, ldx)) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GLM);
   const int nb = glm_launch<4>(ctx->stream, y, x, R, M, ldx, bc, ws, C);
   smg_reduce_partials(ctx, ws, nb, M + C, out, 0);

@@ -616,7 +616,7 @@ inline auto poisson_log_glm_lpmf(const std::vector<int>& y, const matrix_d& x,
 template <bool propto = false, int RY, typename T_alpha, typename T_b, int RB, typename T_scale>
 inline auto normal_id_glm_lpdf(const Eigen::Matrix<double, RY, 1>& y, const matrix_d& x, const T_alpha& alpha,
                                const Eigen::Matrix<T_b, RB, 1>& beta, const T_scale& sigma) {
-  internal::normal_glm_check_scale(internal::glm_sigma_val(sigma));  // first, as the device form
+  internal::glm_check_positive_finite("normal_id_glm_lpdf", "Scale vector", internal::glm_sigma_val(sigma));  // first
   std::vector<T_b> b(beta.data(), beta.data() + beta.size());
   std::vector<double> yv(y.data(), y.data() + y.size());
   std::vector<double> xv(x.data(), x.data() + x.size());

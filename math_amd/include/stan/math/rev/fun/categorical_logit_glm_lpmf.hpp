@@ -24,7 +24,7 @@
 // Row shards (glm_shard) all-reduce the 1 + C + M C sums over RCCL like the
 // other GLM reducers.
 
-#include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/glm_common.hpp>
 #include <stan/math/rev/fun/multiply.hpp>
 
 #include <algorithm>
@@ -37,61 +37,6 @@
 namespace stan {
 namespace math {
 namespace internal {
-
-inline void glm_size_mismatch(const char* fn, const char* name, long long got, long long want) {
-  std::ostringstream m;
-  m << fn << ": " << name << " has dimension = " << got << ", expecting dimension = " << want
-    << "; a function was called with arguments of different scalar, array, vector, or matrix "
-       "types, and they were not consistently sized;  all arguments must be scalars or "
-       "multidimensional values of the same shape.";
-  throw std::invalid_argument(m.str());
-}
-
-// check_finite on a device matrix (column-major, ld): the first non-finite
-// entry by linear index (error path only: host copy column by column)
-inline void glm_check_finite_dev(const char* fn, const char* name, const double* d, long long rows,
-                                 long long cols, long long ld) {
-  std::vector<double> h(size_t(rows > 0 ? rows : 0));
-  for (long long j = 0; j < cols; ++j) {
-    if (rows > 0) amd::to_host(h.data(), d + j * ld, size_t(rows));
-    for (long long i = 0; i < rows; ++i)
-      if (!std::isfinite(h[size_t(i)])) {
-        std::ostringstream m;
-        m << fn << ": " << name << "[" << j * rows + i + 1 << "] is " << h[size_t(i)] << ", but must be finite!";
-        throw std::domain_error(m.str());
-      }
-  }
-}
-
-// check_bounded's message for the first y outside [lo, hi]; row0: the shard's
-// first global row (indices are global).  A rank whose own rows are all in
-// support (the flag came from another rank's shard) throws a message naming
-// no element.
-inline void glm_throw_out_of_support(const char* fn, const int* y, long long n, int lo, int hi,
-                                     long long row0 = 0) {
-  smg_ctx* c = amd::ctx();
-  const long long chunk = 1 << 20;
-  std::vector<int> h(size_t(n > chunk ? chunk : (n > 0 ? n : 0)));
-  for (long long i0 = 0; i0 < n; i0 += chunk) {
-    const long long k = std::min(chunk, n - i0);
-    void* stage = smg_host_scratch(c, size_t(k) * sizeof(int));
-    if (!stage) throw std::bad_alloc();
-    amd::check(smg_memcpy_d2h(c, stage, y + i0, size_t(k) * sizeof(int)), fn);
-    amd::check(smg_sync(c), fn);
-    __builtin_memcpy(h.data(), stage, size_t(k) * sizeof(int));
-    for (long long i = 0; i < k; ++i)
-      if (h[size_t(i)] < lo || h[size_t(i)] > hi) {
-        std::ostringstream m;
-        m << fn << ": categorical outcome out of support[" << row0 + i0 + i + 1 << "] is " << h[size_t(i)]
-          << ", but must be in the interval [" << lo << ", " << hi << "]";
-        throw std::domain_error(m.str());
-      }
-  }
-  std::ostringstream m;
-  m << fn << ": categorical outcome out of support (on another rank's rows), but must be in the interval ["
-    << lo << ", " << hi << "]";
-  throw std::domain_error(m.str());
-}
 
 /** One node over device alpha (C) and beta (M x C); out = [lp, alpha', beta']
  * on the device. */
@@ -169,40 +114,17 @@ struct glm_cat_is_var : std::is_same<T, dev_var_matrix> {};
 /** Device-resident (y, x) row block; alpha (C) and beta (M x C) device
  * operands (dev_var_matrix or dev_data<double>). */
 template <bool propto, typename T_alpha, typename T_beta>
-inline typename std::conditional<internal::glm_cat_is_var<T_alpha>::value ||
-                                     internal::glm_cat_is_var<T_beta>::value,
-                                 var, double>::type
-categorical_logit_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta) {
-  const internal::glm_result r =
-      internal::categorical_glm_eval<propto>(s, internal::operand(alpha), internal::operand(beta));
-  if constexpr (internal::glm_cat_is_var<T_alpha>::value || internal::glm_cat_is_var<T_beta>::value) {
-    if (r.node) return var(r.node);
-    return var(r.lp);
-  } else {
-    return r.lp;
-  }
+inline auto categorical_logit_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta) {
+  return internal::glm_return<internal::glm_cat_is_var<T_alpha>::value || internal::glm_cat_is_var<T_beta>::value>(
+      internal::categorical_glm_eval<propto>(s, internal::operand(alpha), internal::operand(beta)));
 }
 
-template <bool propto, typename T_alpha, typename T_beta>
+template <bool propto = false, typename T_alpha, typename T_beta>
 inline auto categorical_logit_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x, const T_alpha& alpha,
                                        const T_beta& beta) {
-  static const char* fn = "categorical_logit_glm_lpmf";
-  if ((long long)y.size() != (long long)x.rows())  // (:57-60)
-    internal::glm_size_mismatch(fn, "Vector of dependent variables", (long long)y.size(), x.rows());
-  glm_shard s;
-  s.y = y.data();
-  s.x = x.data();
-  s.rows = x.rows();
-  s.M = x.cols();
-  s.ldx = x.rows() > 0 ? x.rows() : 1;
-  s.total_rows = s.rows;
+  glm_shard s = internal::glm_shard_of("categorical_logit_glm_lpmf", y, x);  // (:57-60)
+  if (s.ldx < 1) s.ldx = 1;
   return categorical_logit_glm_lpmf<propto>(s, alpha, beta);
-}
-
-template <typename T_alpha, typename T_beta>
-inline auto categorical_logit_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x, const T_alpha& alpha,
-                                       const T_beta& beta) {
-  return categorical_logit_glm_lpmf<false>(y, x, alpha, beta);
 }
 
 }  // namespace math

@@ -38,14 +38,10 @@
 // bernoulli_logit_glm_lpmf.hpp).
 // Not provided: vector phi, M > 256, the fvar<var> tangent.
 
-#include <stan/math/rev/fun/normal_id_glm_lpdf.hpp>
-#include <stan/math/rev/fun/poisson_log_glm_lpmf.hpp>
+#include <stan/math/rev/fun/glm_common.hpp>
 
 #include <climits>
 #include <cmath>
-#include <sstream>
-#include <stdexcept>
-#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -53,32 +49,11 @@ namespace stan {
 namespace math {
 namespace internal {
 
-// check_positive_finite(function, "Precision parameter", phi)
-inline void neg_binomial_glm_check_precision(const char* fn, double phi) {
-  if (!(phi > 0)) {
-    std::ostringstream m;
-    m << fn << ": Precision parameter is " << phi << ", but must be > 0!";
-    throw std::domain_error(m.str());
-  }
-  if (!std::isfinite(phi)) {
-    std::ostringstream m;
-    m << fn << ": Precision parameter is " << phi << ", but must be finite!";
-    throw std::domain_error(m.str());
-  }
-}
-
 template <bool propto>
 inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p, double phi, vari* phi_vi) {
   static const char* fn = "neg_binomial_2_log_glm_lpmf";
   const int M = s.M;
-  if (int(p.beta.size()) != M) {
-    std::ostringstream m;
-    m << fn << ": Weight vector has dimension = " << p.beta.size() << ", expecting dimension = " << M
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
+  if (int(p.beta.size()) != M) glm_size_mismatch(fn, "Weight vector", (long long)p.beta.size(), M);
   glm_check_alpha_size(fn, p, s.rows);
   smg_ctx* c = amd::ctx();
   // [alpha, beta(M), phi | out: A, alpha', beta'(M), B, C, D, phi' | flag]
@@ -109,25 +84,13 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
   amd::to_host(h.data(), buf, h.size());
   const double* o = h.data() + M + 2;
   if (o[M + 6] != 0.0) glm_throw_negative_y(fn, s.y, s.rows, s.row0, "Failures variables");
-  neg_binomial_glm_check_precision(fn, phi);
+  glm_check_positive_finite(fn, "Precision parameter", phi);
   if (!run) return glm_result{};
   // the stable forms keep theta' finite at theta = +-inf, where alpha' alone
   // would pass; B = sum y theta is non-finite whenever a theta is (0 inf = NaN)
   if (!std::isfinite(o[1]) || !std::isfinite(o[M + 2]) || !std::isfinite(o[0])) {
-    for (int j = 0; j < M; ++j)
-      if (!std::isfinite(p.beta[j])) {
-        std::ostringstream m;
-        m << fn << ": Weight vector[" << j + 1 << "] is " << p.beta[j] << ", but must be finite!";
-        throw std::domain_error(m.str());
-      }
-    if (!std::isfinite(p.alpha)) {
-      std::ostringstream m;
-      m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
-      throw std::domain_error(m.str());
-    }
-    glm_throw_nonfinite_alpha_vec(fn, p, va);
-    throw std::domain_error(std::string(fn) +
-                            ": Matrix of independent variables is not finite, but must be finite!");
+    glm_throw_nonfinite_operands(fn, p, va);
+    glm_throw_nonfinite_x(fn);
   }
   const double N = double(s.distributed ? s.total_rows : s.rows);
   double lp = 0.0;
@@ -140,86 +103,37 @@ inline glm_result neg_binomial_glm_eval(const glm_shard& s, const glm_params& p,
   for (int j = 0; j <= M; ++j) g[j] = o[1 + j];
   g[M + 1] = o[M + 5];
   if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, phi_vi, g, out + 2, M)};
-  return glm_result{lp, new glm_sigma_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, phi_vi, g, out + 2, M)};
+  return glm_result{lp, new glm_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, phi_vi, g, out + 2, M, fn)};
 }
 
 }  // namespace internal
 
 /** Device-resident (y, x) row block. */
-template <bool propto, typename T_alpha, typename T_beta, typename T_precision>
-inline typename std::conditional<internal::glm_is_var<T_alpha>::value ||
-                                     internal::glm_is_var<T_beta>::value ||
-                                     std::is_same<T_precision, var>::value,
-                                 var, double>::type
-neg_binomial_2_log_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta,
-                            const T_precision& phi) {
+template <bool propto = false, typename T_alpha, typename T_beta, typename T_precision>
+inline auto neg_binomial_2_log_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta,
+                                        const T_precision& phi) {
   internal::glm_params p;
   internal::glm_alpha(p, alpha);
   internal::glm_beta(p, beta);
-  const internal::glm_result r = internal::neg_binomial_glm_eval<propto>(
-      s, p, internal::glm_sigma_val(phi), internal::glm_sigma_vi(phi));
-  if constexpr (internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value ||
-                std::is_same<T_precision, var>::value) {
-    if (r.node) return var(r.node);
-    return var(r.lp);
-  } else {
-    return r.lp;
-  }
+  return internal::glm_return<internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value ||
+                              std::is_same<T_precision, var>::value>(
+      internal::neg_binomial_glm_eval<propto>(s, p, internal::glm_sigma_val(phi), internal::glm_sigma_vi(phi)));
 }
 
-template <typename T_alpha, typename T_beta, typename T_precision>
-inline auto neg_binomial_2_log_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta,
-                                        const T_precision& phi) {
-  return neg_binomial_2_log_glm_lpmf<false>(s, alpha, beta, phi);
-}
-
-template <bool propto, typename T_alpha, typename T_beta, typename T_precision>
+template <bool propto = false, typename T_alpha, typename T_beta, typename T_precision>
 inline auto neg_binomial_2_log_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x,
                                         const T_alpha& alpha, const T_beta& beta, const T_precision& phi) {
-  static const char* fn = "neg_binomial_2_log_glm_lpmf";
-  if ((long long)y.size() != (long long)x.rows()) {
-    std::ostringstream m;
-    m << fn << ": Vector of dependent variables has dimension = " << y.size()
-      << ", expecting dimension = " << x.rows()
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
-  glm_shard s;
-  s.y = y.data();
-  s.x = x.data();
-  s.rows = x.rows();
-  s.M = x.cols();
-  s.ldx = x.rows();
-  s.total_rows = s.rows;
-  return neg_binomial_2_log_glm_lpmf<propto>(s, alpha, beta, phi);
-}
-
-template <typename T_alpha, typename T_beta, typename T_precision>
-inline auto neg_binomial_2_log_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x,
-                                        const T_alpha& alpha, const T_beta& beta, const T_precision& phi) {
-  return neg_binomial_2_log_glm_lpmf<false>(y, x, alpha, beta, phi);
+  return neg_binomial_2_log_glm_lpmf<propto>(internal::glm_shard_of("neg_binomial_2_log_glm_lpmf", y, x), alpha,
+                                             beta, phi);
 }
 
 /** Host data (uploaded per call, like the reference reading host memory). */
-template <bool propto, typename T_alpha, typename T_beta, typename T_precision>
+template <bool propto = false, typename T_alpha, typename T_beta, typename T_precision>
 inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor,
                                         int M, const T_alpha& alpha, const T_beta& beta,
                                         const T_precision& phi) {
-  const int R = int(y.size());
-  if ((long long)x_colmajor.size() != (long long)R * M)
-    throw std::invalid_argument("neg_binomial_2_log_glm_lpmf: x must hold y.size() * M values");
-  dev_data<int> yd = to_dev_data(y);
-  dev_data<double> xd = to_dev_data(x_colmajor.data(), x_colmajor.size(), R, M);
-  return neg_binomial_2_log_glm_lpmf<propto>(yd, xd, alpha, beta, phi);
-}
-
-template <typename T_alpha, typename T_beta, typename T_precision>
-inline auto neg_binomial_2_log_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor,
-                                        int M, const T_alpha& alpha, const T_beta& beta,
-                                        const T_precision& phi) {
-  return neg_binomial_2_log_glm_lpmf<false>(y, x_colmajor, M, alpha, beta, phi);
+  const auto d = internal::glm_upload("neg_binomial_2_log_glm_lpmf", y, x_colmajor, M);
+  return neg_binomial_2_log_glm_lpmf<propto>(d.y, d.x, alpha, beta, phi);
 }
 
 }  // namespace math

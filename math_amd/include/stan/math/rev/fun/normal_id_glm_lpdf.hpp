@@ -19,7 +19,7 @@
 // Row shards (glm_shard with yd set) all-reduce the M + 2 sums over RCCL like
 // bernoulli_logit_glm_lpmf; N is then the global row count.
 
-#include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/glm_common.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -31,38 +31,6 @@
 namespace stan {
 namespace math {
 namespace internal {
-
-/** One node over (alpha, beta, sigma): partials g = [alpha', beta'(M), sigma']
- * on the host (arena), beta' also on the device for device-resident beta. */
-class glm_sigma_dev_vari : public local_adjoint_vari {
- public:
-  vari* alpha_vi_;
-  vari** beta_vi_;
-  dev_matrix_vari* beta_dev_;
-  vari* sigma_vi_;
-  double* g_;
-  const double* g_dev_;
-  int M_;
-  glm_sigma_dev_vari(double lp, vari* a, vari** b, dev_matrix_vari* bd, vari* s, double* g,
-                     const double* gd, int M)
-      : local_adjoint_vari(lp), alpha_vi_(a), beta_vi_(b), beta_dev_(bd), sigma_vi_(s), g_(g), g_dev_(gd), M_(M) {}
-  bool touches_adjoints_in(const vari* lo, const vari* hi) const override {
-    auto in = [&](const vari* v) { return v && v >= lo && v < hi; };
-    if (in(alpha_vi_) || in(sigma_vi_)) return true;
-    if (beta_vi_)
-      for (int j = 0; j < M_; ++j)
-        if (in(beta_vi_[j])) return true;
-    return false;
-  }
-  void chain() override {
-    if (alpha_vi_) alpha_vi_->adj_ += adj_ * g_[0];
-    if (beta_vi_)
-      for (int j = 0; j < M_; ++j) beta_vi_[j]->adj_ += adj_ * g_[1 + j];
-    if (beta_dev_)
-      amd::check(smg_axpy(amd::ctx(), M_, adj_, g_dev_, 1, beta_dev_->adj(), 1), "normal_id_glm_lpdf");
-    if (sigma_vi_) sigma_vi_->adj_ += adj_ * g_[M_ + 1];
-  }
-};
 
 // first non-finite y (host copy: error path only) -> check_finite's message
 inline void glm_throw_nonfinite_y(const char* fn, const double* y, long long n, long long row0 = 0) {
@@ -80,35 +48,13 @@ inline void glm_throw_nonfinite_y(const char* fn, const double* y, long long n, 
     }
 }
 
-// check_positive_finite(function, "Scale vector", sigma) (:58)
-inline void normal_glm_check_scale(double sigma) {
-  static const char* fn = "normal_id_glm_lpdf";
-  if (!(sigma > 0)) {
-    std::ostringstream m;
-    m << fn << ": Scale vector is " << sigma << ", but must be > 0!";
-    throw std::domain_error(m.str());
-  }
-  if (!std::isfinite(sigma)) {
-    std::ostringstream m;
-    m << fn << ": Scale vector is " << sigma << ", but must be finite!";
-    throw std::domain_error(m.str());
-  }
-}
-
 template <bool propto>
 inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, double sigma,
                                   vari* sigma_vi) {
   static const char* fn = "normal_id_glm_lpdf";
-  normal_glm_check_scale(sigma);
+  glm_check_positive_finite(fn, "Scale vector", sigma);  // first (:58)
   const int M = s.M;
-  if (int(p.beta.size()) != M) {
-    std::ostringstream m;
-    m << fn << ": Weight vector has dimension = " << p.beta.size() << ", expecting dimension = " << M
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
+  if (int(p.beta.size()) != M) glm_size_mismatch(fn, "Weight vector", (long long)p.beta.size(), M);
   glm_check_alpha_size(fn, p, s.rows);
   const bool any_var = p.any_var() || sigma_vi;
   if (s.total_rows == 0 || (propto && !any_var)) return glm_result{};
@@ -136,18 +82,7 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
   const double sq = h[M + 2];
   if (!std::isfinite(sq)) {  // (:130-136)
     glm_throw_nonfinite_y(fn, s.yd, s.rows, s.row0);
-    for (int j = 0; j < M; ++j)
-      if (!std::isfinite(p.beta[j])) {
-        std::ostringstream m;
-        m << fn << ": Weight vector[" << j + 1 << "] is " << p.beta[j] << ", but must be finite!";
-        throw std::domain_error(m.str());
-      }
-    if (!std::isfinite(p.alpha)) {
-      std::ostringstream m;
-      m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
-      throw std::domain_error(m.str());
-    }
-    glm_throw_nonfinite_alpha_vec(fn, p, va);
+    glm_throw_nonfinite_operands(fn, p, va);
     std::ostringstream m;
     m << fn << ": Matrix of independent variables is " << sq << ", but must be finite!";
     throw std::domain_error(m.str());
@@ -162,84 +97,36 @@ inline glm_result normal_glm_eval(const glm_shard& s, const glm_params& p, doubl
   for (int j = 0; j <= M; ++j) g[j] = h[M + 3 + j];
   g[M + 1] = (sq - N) / sigma;
   if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, sigma_vi, g, out + 2, M)};
-  return glm_result{lp, new glm_sigma_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, sigma_vi, g,
-                                               out + 2, M)};
+  return glm_result{lp, new glm_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, sigma_vi, g, out + 2, M, fn)};
 }
-
-inline double glm_sigma_val(double s) { return s; }
-inline double glm_sigma_val(const var& s) { return s.val(); }
-inline vari* glm_sigma_vi(double) { return nullptr; }
-inline vari* glm_sigma_vi(const var& s) { return s.vi_; }
 
 }  // namespace internal
 
 /** Device-resident (y, x) row block: shard.yd (double y), shard.x. */
 template <bool propto, typename T_alpha, typename T_beta, typename T_scale>
-inline typename std::conditional<internal::glm_is_var<T_alpha>::value ||
-                                     internal::glm_is_var<T_beta>::value ||
-                                     std::is_same<T_scale, var>::value,
-                                 var, double>::type
-normal_id_glm_lpdf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
+inline auto normal_id_glm_lpdf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
   internal::glm_params p;
   internal::glm_alpha(p, alpha);
   internal::glm_beta(p, beta);
-  const internal::glm_result r = internal::normal_glm_eval<propto>(
-      s, p, internal::glm_sigma_val(sigma), internal::glm_sigma_vi(sigma));
-  if constexpr (internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value ||
-                std::is_same<T_scale, var>::value) {
-    if (r.node) return var(r.node);
-    return var(r.lp);
-  } else {
-    return r.lp;
-  }
+  return internal::glm_return<internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value ||
+                              std::is_same<T_scale, var>::value>(
+      internal::normal_glm_eval<propto>(s, p, internal::glm_sigma_val(sigma), internal::glm_sigma_vi(sigma)));
 }
 
-template <bool propto, typename T_alpha, typename T_beta, typename T_scale>
+template <bool propto = false, typename T_alpha, typename T_beta, typename T_scale>
 inline auto normal_id_glm_lpdf(const dev_data<double>& y, const dev_data<double>& x,
                                const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
   static const char* fn = "normal_id_glm_lpdf";
-  internal::normal_glm_check_scale(internal::glm_sigma_val(sigma));  // first (:58)
-  if ((long long)y.size() != (long long)x.rows()) {
-    std::ostringstream m;
-    m << fn << ": Vector of dependent variables has dimension = " << y.size()
-      << ", expecting dimension = " << x.rows()
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
-  glm_shard s;
-  s.yd = y.data();
-  s.x = x.data();
-  s.rows = x.rows();
-  s.M = x.cols();
-  s.ldx = x.rows();
-  s.total_rows = s.rows;
-  return normal_id_glm_lpdf<propto>(s, alpha, beta, sigma);
-}
-
-template <typename T_alpha, typename T_beta, typename T_scale>
-inline auto normal_id_glm_lpdf(const dev_data<double>& y, const dev_data<double>& x,
-                               const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
-  return normal_id_glm_lpdf<false>(y, x, alpha, beta, sigma);
+  internal::glm_check_positive_finite(fn, "Scale vector", internal::glm_sigma_val(sigma));  // first (:58)
+  return normal_id_glm_lpdf<propto>(internal::glm_shard_of(fn, y, x), alpha, beta, sigma);
 }
 
 /** Host data (uploaded per call, like the reference reading host memory). */
-template <bool propto, typename T_alpha, typename T_beta, typename T_scale>
+template <bool propto = false, typename T_alpha, typename T_beta, typename T_scale>
 inline auto normal_id_glm_lpdf(const std::vector<double>& y, const std::vector<double>& x_colmajor,
                                int M, const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
-  const int R = int(y.size());
-  if ((long long)x_colmajor.size() != (long long)R * M)
-    throw std::invalid_argument("normal_id_glm_lpdf: x must hold y.size() * M values");
-  dev_data<double> yd = to_dev_data(y);
-  dev_data<double> xd = to_dev_data(x_colmajor.data(), x_colmajor.size(), R, M);
-  return normal_id_glm_lpdf<propto>(yd, xd, alpha, beta, sigma);
-}
-
-template <typename T_alpha, typename T_beta, typename T_scale>
-inline auto normal_id_glm_lpdf(const std::vector<double>& y, const std::vector<double>& x_colmajor,
-                               int M, const T_alpha& alpha, const T_beta& beta, const T_scale& sigma) {
-  return normal_id_glm_lpdf<false>(y, x_colmajor, M, alpha, beta, sigma);
+  const auto d = internal::glm_upload("normal_id_glm_lpdf", y, x_colmajor, M);
+  return normal_id_glm_lpdf<propto>(d.y, d.x, alpha, beta, sigma);
 }
 
 }  // namespace math

@@ -34,8 +34,7 @@
 // surfaces as an exception), a vector of cut-point vectors, the fvar<var>
 // tangent.
 
-#include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
-#include <stan/math/rev/fun/categorical_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/glm_common.hpp>
 
 #include <cmath>
 #include <sstream>
@@ -163,14 +162,8 @@ inline glm_result ordered_glm_eval(const glm_shard& s, const glm_params& p, cons
   bool finite = true;
   for (int j = 0; j < M + C; ++j) finite = finite && std::isfinite(o[j]);
   if (!finite) {
-    for (int j = 0; j < M; ++j)
-      if (!std::isfinite(p.beta[j])) {
-        std::ostringstream m;
-        m << fn << ": Weight vector[" << j + 1 << "] is " << p.beta[j] << ", but must be finite!";
-        throw std::domain_error(m.str());
-      }
-    throw std::domain_error(std::string(fn) +
-                            ": Matrix of independent variables is not finite, but must be finite!");
+    glm_throw_nonfinite_operands(fn, p, glm_vec_alpha());  // (no intercept: beta alone)
+    glm_throw_nonfinite_x(fn);
   }
   const double lp = o[0];
   if (!any_var) return glm_result{lp, nullptr};
@@ -182,66 +175,28 @@ inline glm_result ordered_glm_eval(const glm_shard& s, const glm_params& p, cons
 }  // namespace internal
 
 /** Device-resident (y, x) row block. */
-template <bool propto, typename T_beta, typename T_cuts>
-inline typename std::conditional<internal::glm_is_var<T_beta>::value || internal::glm_is_var<T_cuts>::value, var,
-                                 double>::type
-ordered_logistic_glm_lpmf(const glm_shard& s, const T_beta& beta, const T_cuts& cuts) {
+template <bool propto = false, typename T_beta, typename T_cuts>
+inline auto ordered_logistic_glm_lpmf(const glm_shard& s, const T_beta& beta, const T_cuts& cuts) {
   internal::glm_params p;
   internal::glm_beta(p, beta);
   internal::glm_cuts cu;
   internal::glm_cuts_of(cu, cuts);
-  const internal::glm_result r = internal::ordered_glm_eval<propto>(s, p, cu);
-  if constexpr (internal::glm_is_var<T_beta>::value || internal::glm_is_var<T_cuts>::value) {
-    if (r.node) return var(r.node);
-    return var(r.lp);
-  } else {
-    return r.lp;
-  }
+  return internal::glm_return<internal::glm_is_var<T_beta>::value || internal::glm_is_var<T_cuts>::value>(
+      internal::ordered_glm_eval<propto>(s, p, cu));
 }
 
-template <typename T_beta, typename T_cuts>
-inline auto ordered_logistic_glm_lpmf(const glm_shard& s, const T_beta& beta, const T_cuts& cuts) {
-  return ordered_logistic_glm_lpmf<false>(s, beta, cuts);
-}
-
-template <bool propto, typename T_beta, typename T_cuts>
+template <bool propto = false, typename T_beta, typename T_cuts>
 inline auto ordered_logistic_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x, const T_beta& beta,
                                       const T_cuts& cuts) {
-  if ((long long)y.size() != (long long)x.rows())
-    internal::glm_size_mismatch("ordered_logistic_glm_lpmf", "Vector of dependent variables", (long long)y.size(),
-                                (long long)x.rows());
-  glm_shard s;
-  s.y = y.data();
-  s.x = x.data();
-  s.rows = x.rows();
-  s.M = x.cols();
-  s.ldx = x.rows();
-  s.total_rows = s.rows;
-  return ordered_logistic_glm_lpmf<propto>(s, beta, cuts);
-}
-
-template <typename T_beta, typename T_cuts>
-inline auto ordered_logistic_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x, const T_beta& beta,
-                                      const T_cuts& cuts) {
-  return ordered_logistic_glm_lpmf<false>(y, x, beta, cuts);
+  return ordered_logistic_glm_lpmf<propto>(internal::glm_shard_of("ordered_logistic_glm_lpmf", y, x), beta, cuts);
 }
 
 /** Host data (uploaded per call, like the reference reading host memory). */
-template <bool propto, typename T_beta, typename T_cuts>
+template <bool propto = false, typename T_beta, typename T_cuts>
 inline auto ordered_logistic_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor, int M,
                                       const T_beta& beta, const T_cuts& cuts) {
-  const int R = int(y.size());
-  if ((long long)x_colmajor.size() != (long long)R * M)
-    throw std::invalid_argument("ordered_logistic_glm_lpmf: x must hold y.size() * M values");
-  dev_data<int> yd = to_dev_data(y);
-  dev_data<double> xd = to_dev_data(x_colmajor.data(), x_colmajor.size(), R, M);
-  return ordered_logistic_glm_lpmf<propto>(yd, xd, beta, cuts);
-}
-
-template <typename T_beta, typename T_cuts>
-inline auto ordered_logistic_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor, int M,
-                                      const T_beta& beta, const T_cuts& cuts) {
-  return ordered_logistic_glm_lpmf<false>(y, x_colmajor, M, beta, cuts);
+  const auto d = internal::glm_upload("ordered_logistic_glm_lpmf", y, x_colmajor, M);
+  return ordered_logistic_glm_lpmf<propto>(d.y, d.x, beta, cuts);
 }
 
 }  // namespace math

@@ -19,59 +19,21 @@
 //   * partials (:102-116): alpha' = sum theta', beta' = x^T theta'.
 // Row shards all-reduce the M + 3 sums over RCCL like bernoulli_logit_glm_lpmf.
 
-#include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
+#include <stan/math/rev/fun/glm_common.hpp>
 
 #include <climits>
-#include <algorithm>
 #include <cmath>
-#include <sstream>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 namespace stan {
 namespace math {
 namespace internal {
 
-// index (global: row0 = the shard's first row) and value of the first
-// negative y (host copy: error path only); a rank whose own rows are all
-// non-negative (the flag came from another rank) names no element.  `name`:
-// the reference's name of y in the message (poisson's by default).
-inline void glm_throw_negative_y(const char* fn, const int* y, long long n, long long row0 = 0,
-                                 const char* name = "Vector of dependent variables") {
-  smg_ctx* c = amd::ctx();
-  const long long chunk = 1 << 20;
-  std::vector<int> h(size_t(n > chunk ? chunk : (n > 0 ? n : 0)));
-  for (long long i0 = 0; i0 < n; i0 += chunk) {
-    const long long k = std::min(chunk, n - i0);
-    void* stage = smg_host_scratch(c, size_t(k) * sizeof(int));
-    if (!stage) throw std::bad_alloc();
-    amd::check(smg_memcpy_d2h(c, stage, y + i0, size_t(k) * sizeof(int)), fn);
-    amd::check(smg_sync(c), fn);
-    __builtin_memcpy(h.data(), stage, size_t(k) * sizeof(int));
-    for (long long i = 0; i < k; ++i)
-      if (h[size_t(i)] < 0) {
-        std::ostringstream m;
-        m << fn << ": " << name << "[" << row0 + i0 + i + 1 << "] is " << h[size_t(i)] << ", but must be >= 0!";
-        throw std::domain_error(m.str());
-      }
-  }
-  throw std::domain_error(std::string(fn) + ": " + name +
-                          " is negative (on another rank's rows), but must be >= 0!");
-}
-
 template <bool propto>
 inline glm_result poisson_glm_eval(const glm_shard& s, const glm_params& p) {
   static const char* fn = "poisson_log_glm_lpmf";
   const int M = s.M;
-  if (int(p.beta.size()) != M) {
-    std::ostringstream m;
-    m << fn << ": Weight vector has dimension = " << p.beta.size() << ", expecting dimension = " << M
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
+  if (int(p.beta.size()) != M) glm_size_mismatch(fn, "Weight vector", (long long)p.beta.size(), M);
   glm_check_alpha_size(fn, p, s.rows);
   smg_ctx* c = amd::ctx();
   // [alpha, beta(M) | out: s, alpha', beta'(M), lgamma sum | flag]
@@ -102,94 +64,41 @@ inline glm_result poisson_glm_eval(const glm_shard& s, const glm_params& p) {
   if (!run) return glm_result{};
   const double sd = h[M + 2];
   if (!std::isfinite(sd)) {  // (:87-91)
-    for (int j = 0; j < M; ++j)
-      if (!std::isfinite(p.beta[j])) {
-        std::ostringstream m;
-        m << fn << ": Weight vector[" << j + 1 << "] is " << p.beta[j] << ", but must be finite!";
-        throw std::domain_error(m.str());
-      }
-    if (!std::isfinite(p.alpha)) {
-      std::ostringstream m;
-      m << fn << ": Intercept is " << p.alpha << ", but must be finite!";
-      throw std::domain_error(m.str());
-    }
-    glm_throw_nonfinite_alpha_vec(fn, p, va);
-    throw std::domain_error(std::string(fn) +
-                            ": Matrix of independent variables is not finite, but must be finite!");
+    glm_throw_nonfinite_operands(fn, p, va);
+    glm_throw_nonfinite_x(fn);
   }
   const double lp = propto ? 0.0 : h[M + 1] - h[2 * M + 3];
   if (!p.any_var()) return glm_result{lp, nullptr};
   double* g = ChainableStack::instance_->memalloc_.alloc_array<double>(size_t(M + 2));
   for (int j = 0; j <= M; ++j) g[j] = h[M + 2 + j];
   if (p.alpha_vec) return glm_result{lp, glm_vec_node(fn, lp, p, va, s.rows, nullptr, g, out + 2, M)};
-  return glm_result{lp, new glm_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, g, out + 2, M)};
+  return glm_result{lp, new glm_dev_vari(lp, p.alpha_vi, p.beta_vi, p.beta_dev, nullptr, g, out + 2, M, fn)};
 }
 
 }  // namespace internal
 
 /** Device-resident (y, x) row block. */
 template <bool propto, typename T_alpha, typename T_beta>
-inline typename std::conditional<internal::glm_is_var<T_alpha>::value ||
-                                     internal::glm_is_var<T_beta>::value,
-                                 var, double>::type
-poisson_log_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta) {
+inline auto poisson_log_glm_lpmf(const glm_shard& s, const T_alpha& alpha, const T_beta& beta) {
   internal::glm_params p;
   internal::glm_alpha(p, alpha);
   internal::glm_beta(p, beta);
-  const internal::glm_result r = internal::poisson_glm_eval<propto>(s, p);
-  if constexpr (internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value) {
-    if (r.node) return var(r.node);
-    return var(r.lp);
-  } else {
-    return r.lp;
-  }
+  return internal::glm_return<internal::glm_is_var<T_alpha>::value || internal::glm_is_var<T_beta>::value>(
+      internal::poisson_glm_eval<propto>(s, p));
 }
 
-template <bool propto, typename T_alpha, typename T_beta>
+template <bool propto = false, typename T_alpha, typename T_beta>
 inline auto poisson_log_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x,
                                  const T_alpha& alpha, const T_beta& beta) {
-  static const char* fn = "poisson_log_glm_lpmf";
-  if ((long long)y.size() != (long long)x.rows()) {
-    std::ostringstream m;
-    m << fn << ": Vector of dependent variables has dimension = " << y.size()
-      << ", expecting dimension = " << x.rows()
-      << "; a function was called with arguments of different scalar, array, vector, or matrix "
-         "types, and they were not consistently sized;  all arguments must be scalars or "
-         "multidimensional values of the same shape.";
-    throw std::invalid_argument(m.str());
-  }
-  glm_shard s;
-  s.y = y.data();
-  s.x = x.data();
-  s.rows = x.rows();
-  s.M = x.cols();
-  s.ldx = x.rows();
-  s.total_rows = s.rows;
-  return poisson_log_glm_lpmf<propto>(s, alpha, beta);
-}
-
-template <typename T_alpha, typename T_beta>
-inline auto poisson_log_glm_lpmf(const dev_data<int>& y, const dev_data<double>& x,
-                                 const T_alpha& alpha, const T_beta& beta) {
-  return poisson_log_glm_lpmf<false>(y, x, alpha, beta);
+  return poisson_log_glm_lpmf<propto>(internal::glm_shard_of("poisson_log_glm_lpmf", y, x), alpha, beta);
 }
 
 /** Host data (uploaded per call, like the reference reading host memory). */
-template <bool propto, typename T_alpha, typename T_beta>
+template <bool propto = false, typename T_alpha, typename T_beta>
 inline auto poisson_log_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor,
                                  int M, const T_alpha& alpha, const T_beta& beta) {
-  const int R = int(y.size());
-  if ((long long)x_colmajor.size() != (long long)R * M)
-    throw std::invalid_argument("poisson_log_glm_lpmf: x must hold y.size() * M values");
-  dev_data<int> yd = to_dev_data(y);
-  dev_data<double> xd = to_dev_data(x_colmajor.data(), x_colmajor.size(), R, M);
-  return poisson_log_glm_lpmf<propto>(yd, xd, alpha, beta);
-}
-
-template <typename T_alpha, typename T_beta>
-inline auto poisson_log_glm_lpmf(const std::vector<int>& y, const std::vector<double>& x_colmajor,
-                                 int M, const T_alpha& alpha, const T_beta& beta) {
-  return poisson_log_glm_lpmf<false>(y, x_colmajor, M, alpha, beta);
+  const auto d = internal::glm_upload("poisson_log_glm_lpmf", y, x_colmajor, M);
+  return poisson_log_glm_lpmf<propto>(d.y, d.x, alpha, beta);
 }
 
 }  // namespace math
