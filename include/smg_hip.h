@@ -855,6 +855,42 @@ int smg_elt_launch_shape(smg_ctx* ctx, int* shape);
  * previous value; any other argument only reads. */
 int smg_elt_set_width(smg_ctx* ctx, int elements);
 
+/* Indexing a device vector by group (math_amd/csrc/index.hip,
+ * rev/fun/index_ops.hpp): the Stan language's u[g] and its transpose, the
+ * per-destination sums.  Indices are 1-based.  The kernels trust g, perm and
+ * offs (the host layer checks the range of every index before it uploads
+ * them); none waits for the host and none uses an atomic.
+ * R == 0 (or J == 0 for smg_segment_sum) is SMG_OK without a launch and with
+ * nothing written; a null ctx, a negative size or a missing buffer is
+ * SMG_ERR_ARG.
+ *
+ * smg_gather: dst[i] = src[g[i]-1] (accumulate == 0) or dst[i] += src[g[i]-1]
+ * for i in [0, R): a streaming map under smg_elt_*'s launch rule, two rows
+ * per lane and trip when dst is on a 16-byte and g on an 8-byte boundary
+ * (smg_elt_set_width forces one or two), the reads of src indexed.
+ *
+ * smg_segment_sum: out[j] (+)= sum_{k = offs[j]}^{offs[j+1]-1} v[perm[k]] for
+ * j in [0, J).  perm (R ints, 0-based rows) lists the rows sorted by
+ * destination, stably; offs (J + 1, offs[0] = 0, offs[J] = R) gives each
+ * destination's range of it.  An empty destination gets 0 when accumulate ==
+ * 0 and is left alone otherwise.  The sorted list is cut into tiles of T
+ * entries (smg_index_launch_shape), one block each, with a fixed-order
+ * segmented sum inside the tile; a destination inside one tile is finished
+ * there, one that crosses tile edges leaves a partial per tile in ws
+ * (smg_segment_sum_ws_doubles(R, J) doubles, device, contents of no use to
+ * the caller) that a further launch on the same stream sums in tile order;
+ * a small launch ahead of both finds each tile's first destination.  The
+ * order of every sum depends on (R, J, offs) only: bitwise repeatable.  R and
+ * J up to 2^31 - 1. */
+int smg_gather(smg_ctx* ctx, const double* src, const int* g, long long R, int accumulate, double* dst);
+long long smg_segment_sum_ws_doubles(long long R, long long J);
+int smg_segment_sum(smg_ctx* ctx, const double* v, const int* perm, const long long* offs, long long R, long long J,
+                    int accumulate, double* ws, double* out);
+/* The launch constants (tests, tools): shape[0..4] = threads of a block and
+ * the tile length T of smg_segment_sum; threads of a block, the grid cap and
+ * the rows per lane and trip (of an aligned call) of smg_gather. */
+int smg_index_launch_shape(smg_ctx* ctx, int* shape);
+
 /* normal_lpdf<propto>(y | mu, sigma) (prim/scal/prob/normal_lpdf.hpp:36-119):
  * each operand is a device vector (stride 1) or scalar (stride 0) of n
  * broadcast elements.  include bits: 1 = NEG_LOG_SQRT_TWO_PI term,

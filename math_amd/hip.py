@@ -154,6 +154,12 @@ _SIGS = {
     "smg_elt_binary_rev": (_I, [_P, _I, _P, _P, _D, _D, _L, _P, _P, _P, _I, _P]),
     "smg_elt_launch_shape": (_I, [_P, ctypes.POINTER(_I)]),
     "smg_elt_set_width": (_I, [_P, _I]),
+    # indexing by group: (ctx, src, g, R, accumulate, dst), (R, J),
+    # (ctx, v, perm, offs, R, J, accumulate, ws, out)
+    "smg_gather": (_I, [_P, _P, _P, _L, _I, _P]),
+    "smg_segment_sum_ws_doubles": (_L, [_L, _L]),
+    "smg_segment_sum": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),
+    "smg_index_launch_shape": (_I, [_P, ctypes.POINTER(_I)]),
     "smg_normal_lpdf": (_I, [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P]),
     "smg_normal_lpdf_fused": (_I, [_P, _P, _P, _P, _D, _D, _D, _L, _I, _P, _P, _P, _P]),
     "smg_student_t_lpdf_fused": (_I, [_P, _P, _P, _P, _P, _D, _D, _D, _D, _L, _I, _P, _P, _P, _P, _P]),

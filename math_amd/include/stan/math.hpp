@@ -24,6 +24,7 @@
 #include <stan/math/rev/fun/log_sum_exp.hpp>
 #include <stan/math/rev/fun/lgamma.hpp>
 #include <stan/math/rev/fun/elt_ops.hpp>
+#include <stan/math/rev/fun/index_ops.hpp>
 #include <stan/math/rev/fun/normal_lpdf.hpp>
 #include <stan/math/rev/fun/student_t_cauchy_lpdf.hpp>
 #include <stan/math/rev/fun/bernoulli_logit_glm_lpmf.hpp>
