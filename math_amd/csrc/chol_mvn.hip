@@ -579,7 +579,7 @@ int smg_gp_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ld
                                long long s_stride, double adj, const double* K0, int ldk, const double* x, int D,
                                double sigma, double l, double* dadj, double* out2) {
   if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (n == 0) {
     if (dadj || out2) {
       const double z[2] = {0.0, 0.0};
@@ -597,20 +597,9 @@ int smg_gp_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ld
   const bool pairs = D == 1 && n % 2 == 0 && ldc % 2 == 0 && ldk % 2 == 0 && (k == 1 || s_stride % 2 == 0) &&
                      ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(s) |
                        reinterpret_cast<uintptr_t>(K0) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL:
-      return gp_inv_adjoint<SMG_GP_EXPONENTIAL>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l,
-                                                dadj, out2);
-    case SMG_GP_MATERN32:
-      return gp_inv_adjoint<SMG_GP_MATERN32>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
-                                             out2);
-    case SMG_GP_MATERN52:
-      return gp_inv_adjoint<SMG_GP_MATERN52>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
-                                             out2);
-    default:
-      return gp_inv_adjoint<SMG_GP_EXP_QUAD>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj,
-                                             out2);
-  }
+  return gp_with_family(family, [&](auto F) {
+    return gp_inv_adjoint<F()>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, K0, ldk, x, D, sigma, l, dadj, out2);
+  });
 }
 
 int smg_gp_cov_inverse_adjoint_x(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
@@ -621,25 +610,14 @@ int smg_gp_cov_inverse_adjoint_x(smg_ctx* ctx, int family, const double* C, int 
     return smg_gp_cov_inverse_adjoint(ctx, family, C, ldc, n, s, k, s_stride, adj, nullptr, ldc, x, D, sigma, l, dadj,
                                       out2);
   if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (!C || !s || !x || ldc < n || !(sigma > 0 && l > 0)) return SMG_ERR_ARG;
   const bool pairs = D == 1 && n % 2 == 0 && ldc % 2 == 0 && (k == 1 || s_stride % 2 == 0) &&
                      ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(s) |
                        reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL:
-      return gp_inv_adjoint<SMG_GP_EXPONENTIAL>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
-                                                dadj, out2);
-    case SMG_GP_MATERN32:
-      return gp_inv_adjoint<SMG_GP_MATERN32>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
-                                             dadj, out2);
-    case SMG_GP_MATERN52:
-      return gp_inv_adjoint<SMG_GP_MATERN52>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
-                                             dadj, out2);
-    default:
-      return gp_inv_adjoint<SMG_GP_EXP_QUAD>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l,
-                                             dadj, out2);
-  }
+  return gp_with_family(family, [&](auto F) {
+    return gp_inv_adjoint<F()>(ctx, pairs, C, ldc, n, s, k, s_stride, adj, nullptr, 0, x, D, sigma, l, dadj, out2);
+  });
 }
 
 int smg_cholesky_inv_t_async(smg_ctx* ctx, const double* L, int ldl, const double* aux, int n, double* ws,

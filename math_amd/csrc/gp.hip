@@ -15,17 +15,20 @@
 // The forward and reverse kernels are templated on the covariance family
 // (gp_family.h: exp_quad, exponential, Matern 3/2 and 5/2); their argument
 // inv_half_sq_l is the family's length-scale coefficient, 1 / (2 l^2) for
-// exp_quad.  The tangent kernels are exp_quad's alone.  The cross-covariance
-// K(x1, x2) (smg_gp_cross_cov_fwd / _rev) is the same walk over a rectangle,
-// without the diagonal.
+// exp_quad.  The tangent kernels are exp_quad's alone.
+//
+// Everything rectangular -- the cross-covariance K(x1, x2) of the four families
+// (smg_gp_cross_cov_fwd / _rev), gp_periodic_cov and gp_dot_prod_cov, square and
+// cross -- is one walk over an n1 x n2 rectangle, without the diagonal
+// (k_gp_rect_*), instantiated with three pair laws (gp_stat_law<F>, gp_per_law,
+// gp_dot_law) and launched by rect_fwd / rect_rev.  Its final pass
+// k_gp_rect_final is the square reverse's too.
 //
 // add_diag: prim/mat/fun/add_diag.hpp:20-55.
 #include "smg_internal.h"
 #include "gp_family.h"
 
 namespace {
-
-constexpr int GP_BLOCKS = 2048;
 
 template <int F>
 __global__ __launch_bounds__(256) void k_gp_fwd(const double* __restrict__ x, int n, double s2,
@@ -122,24 +125,6 @@ __global__ __launch_bounds__(256) void k_gp_rev_partials_col2(const double* __re
   if (threadIdx.x == 0) {
     part[2 * blockIdx.x + 0] = ss;
     part[2 * blockIdx.x + 1] = sl;
-  }
-}
-
-template <int F>
-__global__ void k_gp_rev_final(const double* __restrict__ part, int nparts, double sigma, double l,
-                               double* out2) {
-  __shared__ double lds[16];
-  double ss = 0.0, sl = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    ss += part[2 * i];
-    sl += part[2 * i + 1];
-  }
-  ss = block_sum(ss, lds);
-  __syncthreads();
-  sl = block_sum(sl, lds);
-  if (threadIdx.x == 0) {
-    out2[0] += ss * 2 / sigma;     // :110
-    out2[1] += gp_fam<F>::lscale(sl, l);  // exp_quad: sl / l^3 (:109)
   }
 }
 
@@ -426,6 +411,343 @@ __global__ __launch_bounds__(256) void k_gp_nd_rev_partials(const double* __rest
   }
 }
 
+// The rectangular walk: K(x1, x2), n1 x n2, and its reverse, for every
+// covariance with rectangular entries (smg_gp_cross_cov_*, the four stationary
+// families; smg_gp_periodic_cov_* and smg_gp_dot_prod_cov_*, whose square
+// K(x, x) is x1 == x2).  It is written once, over a pair law passed by value
+// that carries its own scalars and provides what the walk cannot know:
+//   q1(xi, xj)      the law's argument q of a pair of scalar points (D == 1)
+//   step(acc, a, b) one coordinate's term of the D > 1 sum, in coordinate order
+//   qn(acc)         q from that sum
+//   k(q)            the element
+//   NS, acc(a, q, sum)   the reverse's NS sums, and one adjoint entry's terms
+//   finish(sum, out)     the last line of the final pass
+// Every position alike, no diagonal branch: a coincident pair gives the
+// diagonal's value exactly, and the sign of a difference drops out of q (the
+// products of the dot law commute), so x1 == x2 gives a bitwise symmetric K.
+
+// (both distance laws: the squared distance, coordinate by coordinate)
+struct gp_sq_dist {
+  static __device__ __forceinline__ void step(double& acc, double a, double b) {
+    const double t = a - b;
+    acc += t * t;
+  }
+};
+
+// Stationary (gp_fam<F>): q and the terms of gp_family.h; the bits of k_gp_fwd*
+// when x1 == x2.
+template <int F>
+struct gp_stat_law : gp_sq_dist {
+  static constexpr int NS = 2;             // [sum Kadj K, l-scaled sum Kadj dK/dl]
+  static constexpr bool RED_DESC = true;   // (the block reduction takes the l sum first)
+  double s2, c, sigma, l;
+  gp_stat_law(double sigma_, double l_) : s2(sigma_ * sigma_), c(gp_fam<F>::coef(l_)), sigma(sigma_), l(l_) {}
+  __device__ __forceinline__ double q1(double xi, double xj) const { return gp_fam<F>::from_diff(xi - xj); }
+  __device__ __forceinline__ double qn(double d2) const { return gp_fam<F>::from_sq(d2); }
+  __device__ __forceinline__ double k(double q) const { return gp_fam<F>::k(q, s2, c); }
+  __device__ __forceinline__ void acc(double a, double q, double* sum) const {
+    gp_fam<F>::acc(a, q, s2, c, sum[0], sum[1]);
+  }
+  __device__ __forceinline__ void finish(const double* sum, double* out) const {
+    out[0] += sum[0] * 2 / sigma;              // :110
+    out[1] += gp_fam<F>::lscale(sum[1], l);    // exp_quad: sl / l^3 (:109)
+  }
+};
+
+// Periodic (gp_periodic_cov, Stan Math 3.0.0 prim/mat/fun/), q = d, a = pi d / p:
+//   K = s2 exp(-2 sin^2(a) / l^2),  dK/dsigma = 2 K / sigma,
+//   dK/dl = K 4 sin^2(a) / l^3,  dK/dp = K (2 pi d / (l^2 p^2)) sin(2a).
+// sin(a) and cos(a) come from one sincospi(d / p) (the forward needs sinpi
+// alone), d / p as d times the host's 1 / p: exact argument reduction, so a
+// pair a whole number of periods apart gives s2 when d / p is exact, and
+// sin(2a) = 2 sin cos.
+struct gp_per_law : gp_sq_dist {
+  static constexpr int NS = 3;  // sums of a K, a K sin^2, a K d sin cos
+  static constexpr bool RED_DESC = false;
+  double s2, inv_p, cn, sigma, l, p;  // cn = -2 / l^2
+  gp_per_law(double sigma_, double l_, double p_)
+      : s2(sigma_ * sigma_), inv_p(1.0 / p_), cn(-2.0 / (l_ * l_)), sigma(sigma_), l(l_), p(p_) {}
+  __device__ __forceinline__ double q1(double xi, double xj) const { return fabs(xi - xj); }
+  __device__ __forceinline__ double qn(double d2) const { return sqrt(d2); }
+  __device__ __forceinline__ double k(double d) const {
+    const double s = sinpi(d * inv_p);
+    return s2 * exp(cn * (s * s));
+  }
+  __device__ __forceinline__ void acc(double a, double d, double* sum) const {
+    double s, c;
+    sincospi(d * inv_p, &s, &c);
+    const double ss = s * s;
+    const double ak = a * (s2 * exp(cn * ss));
+    sum[0] += ak;
+    sum[1] += ak * ss;
+    sum[2] += ak * (d * (s * c));
+  }
+  // out3 += [2 ss / sigma, 4 sl / l^3, 4 pi sp / (l^2 p^2)] (sp carries sin cos = sin(2a) / 2)
+  __device__ __forceinline__ void finish(const double* sum, double* out) const {
+    out[0] += sum[0] * 2 / sigma;
+    out[1] += 4 * sum[1] / (l * l * l);
+    out[2] += 4 * 3.14159265358979323846 * sum[2] / (l * l * p * p);
+  }
+};
+
+// Dot product (gp_dot_prod_cov): K_ij = sigma^2 + sum_d x1_id x2_jd, q the sum
+// of products; dK/dsigma = 2 sigma, so the reverse is the sum of the adjoint
+// and reads no points (k_gp_dot_rev_partials* below, not the walk's acc).
+struct gp_dot_law {
+  static constexpr int NS = 1;
+  static constexpr bool RED_DESC = false;
+  double s2, sigma;
+  explicit gp_dot_law(double sigma_) : s2(sigma_ * sigma_), sigma(sigma_) {}
+  __device__ __forceinline__ double q1(double xi, double xj) const { return xi * xj; }
+  static __device__ __forceinline__ void step(double& acc, double a, double b) { acc += a * b; }
+  __device__ __forceinline__ double qn(double dot) const { return dot; }
+  __device__ __forceinline__ double k(double dot) const { return s2 + dot; }
+  __device__ __forceinline__ void finish(const double* sum, double* out) const { out[0] += 2 * sigma * sum[0]; }
+};
+
+// The walk of k_gp_fwd_col2 / k_gp_nd_fwd over the rectangle: a workgroup walks
+// whole columns j (x2_j in a register for D == 1, staged in LDS otherwise), its
+// lanes consecutive rows i of x1.  The grid's y dimension splits the rows
+// (blockIdx.y takes every gridDim.y-th pass of a workgroup's rows), so that a
+// tall K with few columns still fills the chip; it is 1 once the columns alone
+// give GP_BLOCKS workgroups (cross_grid, gp_family.h).
+//
+// Column form: 16-byte aligned x1 and columns, even n1 and ldk (col2_ok)
+template <class Law>
+__global__ __launch_bounds__(256) void k_gp_rect_fwd_col2(Law law, const double* __restrict__ x1, int n1,
+                                                          const double* __restrict__ x2, int n2,
+                                                          double* __restrict__ K, int ldk) {
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          const double2 xi = xr[p];
+          double2 v;
+          v.x = law.k(law.q1(xi.x, xj));
+          v.y = law.k(law.q1(xi.y, xj));
+          col[p] = v;
+        }
+      }
+    }
+  }
+}
+
+// Generic form: any n1 and ldk (rows n1 .. ldk - 1 are not written)
+template <class Law>
+__global__ __launch_bounds__(256) void k_gp_rect_fwd(Law law, const double* __restrict__ x1, int n1,
+                                                     const double* __restrict__ x2, int n2, double* __restrict__ K,
+                                                     int ldk) {
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    double* col = K + (size_t)j * ldk;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) col[i] = law.k(law.q1(x1[i], xj));
+  }
+}
+
+template <class Law>
+__global__ __launch_bounds__(256) void k_gp_rect_nd_fwd(Law law, const double* __restrict__ x1, int n1,
+                                                        const double* __restrict__ x2, int n2, int D,
+                                                        double* __restrict__ K, int ldk) {
+  extern __shared__ double xj[];
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double* xi = x1 + (size_t)i * D;
+      double acc = 0.0;
+      for (int d = 0; d < D; ++d) Law::step(acc, xi[d], xj[d]);
+      K[i + (size_t)j * ldk] = law.k(law.qn(acc));
+    }
+  }
+}
+
+// A workgroup's NS sums -> part[NS b ..], b its place in the grid
+template <int NS, bool RED_DESC>
+__device__ __forceinline__ void rect_store_partials(const double* sum, double* lds, double* __restrict__ part) {
+  double tot[NS];
+#pragma unroll
+  for (int r = 0; r < NS; ++r) {
+    const int s = RED_DESC ? NS - 1 - r : r;
+    if (r) __syncthreads();
+    tot[s] = block_sum(sum[s], lds);
+  }
+  if (threadIdx.x == 0) {
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) part[NS * b + s] = tot[s];
+  }
+}
+
+// The reverse's per-workgroup partials over the same walks (one read of Kadj,
+// K recomputed); k_gp_rect_final sums them.
+template <class Law>
+__global__ __launch_bounds__(256) void k_gp_rect_rev_partials_col2(Law law, const double* __restrict__ x1, int n1,
+                                                                   const double* __restrict__ x2, int n2,
+                                                                   const double* __restrict__ Ka, int lda,
+                                                                   double* __restrict__ part) {
+  __shared__ double lds[16];
+  const int np = n1 >> 1;
+  const double2* xr = reinterpret_cast<const double2*>(x1);
+  double sum[Law::NS];
+#pragma unroll
+  for (int s = 0; s < Law::NS; ++s) sum[s] = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double xj = x2[j];
+    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+      double2 a[4], xi[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          a[k] = col[p];
+          xi[k] = xr[p];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        if (p < np) {
+          law.acc(a[k].x, law.q1(xi[k].x, xj), sum);
+          law.acc(a[k].y, law.q1(xi[k].y, xj), sum);
+        }
+      }
+    }
+  }
+  rect_store_partials<Law::NS, Law::RED_DESC>(sum, lds, part);
+}
+
+// Generic form, D >= 1 (x2_j staged in LDS as k_gp_rect_nd_fwd does; D == 1 from the two scalars)
+template <class Law>
+__global__ __launch_bounds__(256) void k_gp_rect_rev_partials(Law law, const double* __restrict__ x1, int n1,
+                                                              const double* __restrict__ x2, int n2, int D,
+                                                              const double* __restrict__ Ka, int lda,
+                                                              double* __restrict__ part) {
+  extern __shared__ double xj[];
+  __shared__ double lds[16];
+  double sum[Law::NS];
+#pragma unroll
+  for (int s = 0; s < Law::NS; ++s) sum[s] = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
+    __syncthreads();
+    const double* col = Ka + (size_t)j * lda;
+    const double xj0 = xj[0];
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
+      const double a = col[i];
+      if (D == 1) {
+        law.acc(a, law.q1(x1[i], xj0), sum);
+      } else {
+        const double* xi = x1 + (size_t)i * D;
+        double acc = 0.0;
+        for (int d = 0; d < D; ++d) Law::step(acc, xi[d], xj[d]);
+        law.acc(a, law.qn(acc), sum);
+      }
+    }
+  }
+  rect_store_partials<Law::NS, Law::RED_DESC>(sum, lds, part);
+}
+
+// The dot product's reverse partials: per-workgroup sums of the n1 x n2 adjoint over the same walks
+__global__ __launch_bounds__(256) void k_gp_dot_rev_partials_col2(int n1, int n2, const double* __restrict__ Ka,
+                                                                  int lda, double* __restrict__ part) {
+  __shared__ double lds[16];
+  const int np = n1 >> 1;
+  double as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
+    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
+      double2 a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = p0 + 256 * k;
+        a[k] = p < np ? col[p] : make_double2(0.0, 0.0);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) as += a[k].x + a[k].y;
+    }
+  }
+  rect_store_partials<1, false>(&as, lds, part);
+}
+
+__global__ __launch_bounds__(256) void k_gp_dot_rev_partials(int n1, int n2, const double* __restrict__ Ka, int lda,
+                                                             double* __restrict__ part) {
+  __shared__ double lds[16];
+  double as = 0.0;
+  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
+    const double* col = Ka + (size_t)j * lda;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) as += col[i];
+  }
+  rect_store_partials<1, false>(&as, lds, part);
+}
+
+// The one ordered pass over the partials (the square reverse's too): out += law.finish(sums)
+template <class Law>
+__global__ void k_gp_rect_final(Law law, const double* __restrict__ part, int nparts, double* out) {
+  __shared__ double lds[16];
+  double sum[Law::NS];
+#pragma unroll
+  for (int s = 0; s < Law::NS; ++s) sum[s] = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+#pragma unroll
+    for (int s = 0; s < Law::NS; ++s) sum[s] += part[Law::NS * i + s];
+  }
+#pragma unroll
+  for (int s = 0; s < Law::NS; ++s) {
+    if (s) __syncthreads();
+    sum[s] = block_sum(sum[s], lds);
+  }
+  if (threadIdx.x == 0) law.finish(sum, out);
+}
+
+// K(x1, x2) of a law for checked arguments, n1, n2 > 0: the LDS-staged form for
+// D > 1, the column form for aligned scalar points, the generic form otherwise
+template <class Law>
+int rect_fwd(smg_ctx* ctx, const Law& law, const double* x1, int n1, const double* x2, int n2, int D, double* K,
+             int ldk) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  if (D > 1)
+    hipLaunchKernelGGL(k_gp_rect_nd_fwd<Law>, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, law,
+                       x1, n1, x2, n2, D, K, ldk);
+  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
+    hipLaunchKernelGGL(k_gp_rect_fwd_col2<Law>, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, law, x1, n1, x2,
+                       n2, K, ldk);
+  else
+    hipLaunchKernelGGL(k_gp_rect_fwd<Law>, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, law, x1, n1, x2, n2, K,
+                       ldk);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
+// out += the law's hyperparameter derivatives of K(x1, x2) from its adjoint (same forms)
+template <class Law>
+int rect_rev(smg_ctx* ctx, const Law& law, const double* x1, int n1, const double* x2, int n2, int D,
+             const double* Kadj, int ldka, double* out) {
+  smg_prof_scope prof(ctx, SMG_FAM_GP);
+  const bool col2 = D == 1 && col2_ok(x1, 2, n1) && col2_ok(Kadj, ldka, n1);
+  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
+  const int nb = (int)(grid.x * grid.y);
+  double* part = smg_ws(ctx, SMG_WS_RED, Law::NS * (size_t)nb);
+  if (!part) return SMG_ERR_OOM;
+  if (col2)
+    hipLaunchKernelGGL(k_gp_rect_rev_partials_col2<Law>, grid, dim3(256), 0, ctx->stream, law, x1, n1, x2, n2, Kadj,
+                       ldka, part);
+  else
+    hipLaunchKernelGGL(k_gp_rect_rev_partials<Law>, grid, dim3(256), D * sizeof(double), ctx->stream, law, x1, n1, x2,
+                       n2, D, Kadj, ldka, part);
+  hipLaunchKernelGGL(k_gp_rect_final<Law>, dim3(1), dim3(1024), 0, ctx->stream, law, part, nb, out);
+  SMG_LAUNCH_CHECK();
+  return SMG_OK;
+}
+
 inline int grid_for(long long tot) {
   long long g = (tot + 255) / 256;
   if (g > 8192) g = 8192;
@@ -476,7 +798,8 @@ int gp_rev(smg_ctx* ctx, const double* x, int D, int n, double sigma, double l, 
     hipLaunchKernelGGL(k_gp_rev_partials_col2<F>, dim3(nb), dim3(256), 0, ctx->stream, x, n, s2, c, Kadj, ldka, part);
   else
     hipLaunchKernelGGL(k_gp_rev_partials<F>, dim3(nb), dim3(256), 0, ctx->stream, x, n, s2, c, Kadj, ldka, part);
-  hipLaunchKernelGGL(k_gp_rev_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
+  hipLaunchKernelGGL(k_gp_rect_final<gp_stat_law<F>>, dim3(1), dim3(1024), 0, ctx->stream, gp_stat_law<F>(sigma, l), part, nb,
+                     out2);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
 }
@@ -586,229 +909,16 @@ int gp_chol_src(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl) {
   return SMG_OK;
 }
 
-// Cross-covariance K(x1, x2), n1 x n2 (smg_gp_cross_cov_fwd / _rev): the walk
-// of k_gp_fwd_col2 / k_gp_nd_fwd over a rectangle.  A workgroup walks whole
-// columns j (x2_j in a register for D == 1, staged in LDS otherwise), its
-// lanes consecutive rows i of x1.  No diagonal branch: every element is the
-// family's expression of x1_i - x2_j, which is s2 exactly at a coincident
-// pair and, the difference's sign dropping out of from_diff / from_sq, the
-// bits of k_gp_fwd* when x1 == x2.  The grid's y dimension splits the rows
-// (blockIdx.y takes every gridDim.y-th pass of a workgroup's rows), so that a
-// tall K with few columns still fills the chip; it is 1 once the columns
-// alone give GP_BLOCKS workgroups (cross_grid).
-template <int F>
-__global__ __launch_bounds__(256) void k_gp_cross_fwd_col2(const double* __restrict__ x1, int n1,
-                                                           const double* __restrict__ x2, int n2, double s2,
-                                                           double c, double* __restrict__ K, int ldk) {
-  const int np = n1 >> 1;
-  const double2* xr = reinterpret_cast<const double2*>(x1);
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          const double2 xi = xr[p];
-          double2 v;
-          v.x = gp_fam<F>::k(gp_fam<F>::from_diff(xi.x - xj), s2, c);
-          v.y = gp_fam<F>::k(gp_fam<F>::from_diff(xi.y - xj), s2, c);
-          col[p] = v;
-        }
-      }
-    }
-  }
-}
-
-// Generic form: any n1 and ldk (rows n1 .. ldk - 1 are not written)
-template <int F>
-__global__ __launch_bounds__(256) void k_gp_cross_fwd(const double* __restrict__ x1, int n1,
-                                                      const double* __restrict__ x2, int n2, double s2, double c,
-                                                      double* __restrict__ K, int ldk) {
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double* col = K + (size_t)j * ldk;
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256)
-      col[i] = gp_fam<F>::k(gp_fam<F>::from_diff(x1[i] - xj), s2, c);
-  }
-}
-
-template <int F>
-__global__ __launch_bounds__(256) void k_gp_cross_nd_fwd(const double* __restrict__ x1, int n1,
-                                                         const double* __restrict__ x2, int n2, int D, double s2,
-                                                         double c, double* __restrict__ K, int ldk) {
-  extern __shared__ double xj[];
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    __syncthreads();
-    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
-    __syncthreads();
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
-      const double* xi = x1 + (size_t)i * D;
-      double d2 = 0.0;
-      for (int d = 0; d < D; ++d) {
-        const double t = xi[d] - xj[d];
-        d2 += t * t;
-      }
-      K[i + (size_t)j * ldk] = gp_fam<F>::k(gp_fam<F>::from_sq(d2), s2, c);
-    }
-  }
-}
-
-// The reverse's per-workgroup partials [sum Kadj K, l-scaled sum Kadj dK/dl]
-// over the same walks (one read of Kadj, K recomputed); k_gp_rev_final sums them.
-template <int F>
-__global__ __launch_bounds__(256) void k_gp_cross_rev_partials_col2(const double* __restrict__ x1, int n1,
-                                                                    const double* __restrict__ x2, int n2,
-                                                                    double s2, double c,
-                                                                    const double* __restrict__ Ka, int lda,
-                                                                    double* __restrict__ part) {
-  __shared__ double lds[16];
-  const int np = n1 >> 1;
-  const double2* xr = reinterpret_cast<const double2*>(x1);
-  double al = 0.0, as = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-      double2 a[4], xi[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          a[k] = col[p];
-          xi[k] = xr[p];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          gp_fam<F>::acc(a[k].x, gp_fam<F>::from_diff(xi[k].x - xj), s2, c, as, al);
-          gp_fam<F>::acc(a[k].y, gp_fam<F>::from_diff(xi[k].y - xj), s2, c, as, al);
-        }
-      }
-    }
-  }
-  const double sl = block_sum(al, lds);
-  __syncthreads();
-  const double ss = block_sum(as, lds);
-  if (threadIdx.x == 0) {
-    const int b = blockIdx.y * gridDim.x + blockIdx.x;
-    part[2 * b + 0] = ss;
-    part[2 * b + 1] = sl;
-  }
-}
-
-// Generic form, D >= 1 (x2_j staged in LDS as k_gp_cross_nd_fwd does; D == 1 from the difference)
-template <int F>
-__global__ __launch_bounds__(256) void k_gp_cross_rev_partials(const double* __restrict__ x1, int n1,
-                                                               const double* __restrict__ x2, int n2, int D,
-                                                               double s2, double c, const double* __restrict__ Ka,
-                                                               int lda, double* __restrict__ part) {
-  extern __shared__ double xj[];
-  __shared__ double lds[16];
-  double al = 0.0, as = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    __syncthreads();
-    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
-    __syncthreads();
-    const double* col = Ka + (size_t)j * lda;
-    const double xj0 = xj[0];
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
-      const double a = col[i];
-      if (D == 1) {
-        gp_fam<F>::acc(a, gp_fam<F>::from_diff(x1[i] - xj0), s2, c, as, al);
-      } else {
-        const double* xi = x1 + (size_t)i * D;
-        double d2 = 0.0;
-        for (int d = 0; d < D; ++d) {
-          const double t = xi[d] - xj[d];
-          d2 += t * t;
-        }
-        gp_fam<F>::acc(a, gp_fam<F>::from_sq(d2), s2, c, as, al);
-      }
-    }
-  }
-  const double sl = block_sum(al, lds);
-  __syncthreads();
-  const double ss = block_sum(as, lds);
-  if (threadIdx.x == 0) {
-    const int b = blockIdx.y * gridDim.x + blockIdx.x;
-    part[2 * b + 0] = ss;
-    part[2 * b + 1] = sl;
-  }
-}
-
-// One workgroup per column up to GP_BLOCKS (the column loop wraps beyond),
-// times as many row parts as bring the grid to about GP_BLOCKS workgroups, none
-// of them without rows; rows: what a workgroup covers in one pass.
-inline dim3 cross_grid(int n1, int n2, int rows) {
-  const int gx = n2 < GP_BLOCKS ? n2 : GP_BLOCKS;
-  int gy = smg_ceil_div(n1, rows);
-  if (gy > GP_BLOCKS / gx) gy = GP_BLOCKS / gx;
-  return dim3(gx, gy < 1 ? 1 : gy);
-}
-
-// K(x1, x2) of family F for checked arguments, n1, n2 > 0
-template <int F>
-int gp_cross_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma, double l,
-                 double* K, int ldk) {
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma;
-  const double c = gp_fam<F>::coef(l);
-  if (D > 1)
-    hipLaunchKernelGGL(k_gp_cross_nd_fwd<F>, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1,
-                       x2, n2, D, s2, c, K, ldk);
-  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
-    hipLaunchKernelGGL(k_gp_cross_fwd_col2<F>, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2,
-                       c, K, ldk);
-  else
-    hipLaunchKernelGGL(k_gp_cross_fwd<F>, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, c, K,
-                       ldk);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
-}
-
-// out2 += [d/dsigma, d/dl] of K(x1, x2) from its adjoint (same forms)
-template <int F>
-int gp_cross_rev(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma, double l,
-                 const double* Kadj, int ldka, double* out2) {
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma;
-  const double c = gp_fam<F>::coef(l);
-  const bool col2 = D == 1 && col2_ok(x1, 2, n1) && col2_ok(Kadj, ldka, n1);
-  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
-  const int nb = (int)(grid.x * grid.y);
-  double* part = smg_ws(ctx, SMG_WS_RED, 2 * (size_t)nb);
-  if (!part) return SMG_ERR_OOM;
-  if (col2)
-    hipLaunchKernelGGL(k_gp_cross_rev_partials_col2<F>, grid, dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, c, Kadj,
-                       ldka, part);
-  else
-    hipLaunchKernelGGL(k_gp_cross_rev_partials<F>, grid, dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2, n2, D,
-                       s2, c, Kadj, ldka, part);
-  hipLaunchKernelGGL(k_gp_rev_final<F>, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, out2);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
-}
-
 }  // namespace
 
 bool smg_gp_source_ok(const smg_gp_source* s) {
-  return s && s->n >= 0 && s->D >= 1 && s->D <= 8192 && s->family >= SMG_GP_EXP_QUAD && s->family <= SMG_GP_MATERN52 &&
-         (s->n == 0 || s->x) && s->sigma > 0 && s->l > 0 && std::isfinite(s->sigma) && std::isfinite(s->l) &&
-         std::isfinite(s->d);
+  return s && s->n >= 0 && s->D >= 1 && s->D <= 8192 && gp_family_ok(s->family) && (s->n == 0 || s->x) &&
+         s->sigma > 0 && s->l > 0 && std::isfinite(s->sigma) && std::isfinite(s->l) && std::isfinite(s->d);
 }
 
 // checked arguments (smg_gp_source_ok, n > 0, L n x n with ldl >= n)
 int smg_gp_chol_source_launch(smg_ctx* ctx, const smg_gp_source* s, double* L, int ldl) {
-  switch (s->family) {
-    case SMG_GP_EXPONENTIAL: return gp_chol_src<SMG_GP_EXPONENTIAL>(ctx, s, L, ldl);
-    case SMG_GP_MATERN32: return gp_chol_src<SMG_GP_MATERN32>(ctx, s, L, ldl);
-    case SMG_GP_MATERN52: return gp_chol_src<SMG_GP_MATERN52>(ctx, s, L, ldl);
-    default: return gp_chol_src<SMG_GP_EXP_QUAD>(ctx, s, L, ldl);
-  }
+  return gp_with_family(s->family, [&](auto F) { return gp_chol_src<F()>(ctx, s, L, ldl); });
 }
 
 extern "C" {
@@ -846,56 +956,38 @@ int smg_gp_exp_quad_cov_nd_rev(smg_ctx* ctx, const double* x, int D, int n, doub
 int smg_gp_cov_fwd(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l, double* K,
                    int ldk) {
   if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !K || ldk < n))) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL: return gp_fwd<SMG_GP_EXPONENTIAL>(ctx, x, D, n, sigma, l, K, ldk);
-    case SMG_GP_MATERN32: return gp_fwd<SMG_GP_MATERN32>(ctx, x, D, n, sigma, l, K, ldk);
-    case SMG_GP_MATERN52: return gp_fwd<SMG_GP_MATERN52>(ctx, x, D, n, sigma, l, K, ldk);
-    default: return gp_fwd<SMG_GP_EXP_QUAD>(ctx, x, D, n, sigma, l, K, ldk);
-  }
+  return gp_with_family(family, [&](auto F) { return gp_fwd<F()>(ctx, x, D, n, sigma, l, K, ldk); });
 }
 
 int smg_gp_cov_rev(smg_ctx* ctx, int family, const double* x, int D, int n, double sigma, double l,
                    const double* Kadj, int ldka, double* out2) {
   if (!ctx || n < 0 || D < 1 || D > 8192 || (n > 0 && (!x || !Kadj || !out2 || ldka < n))) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL: return gp_rev<SMG_GP_EXPONENTIAL>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
-    case SMG_GP_MATERN32: return gp_rev<SMG_GP_MATERN32>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
-    case SMG_GP_MATERN52: return gp_rev<SMG_GP_MATERN52>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
-    default: return gp_rev<SMG_GP_EXP_QUAD>(ctx, x, D, n, sigma, l, Kadj, ldka, out2);
-  }
+  return gp_with_family(family, [&](auto F) { return gp_rev<F()>(ctx, x, D, n, sigma, l, Kadj, ldka, out2); });
 }
 
 int smg_gp_cross_cov_fwd(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
                          double sigma, double l, double* K, int ldk) {
   if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL: return gp_cross_fwd<SMG_GP_EXPONENTIAL>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
-    case SMG_GP_MATERN32: return gp_cross_fwd<SMG_GP_MATERN32>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
-    case SMG_GP_MATERN52: return gp_cross_fwd<SMG_GP_MATERN52>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
-    default: return gp_cross_fwd<SMG_GP_EXP_QUAD>(ctx, x1, n1, x2, n2, D, sigma, l, K, ldk);
-  }
+  return gp_with_family(
+      family, [&](auto F) { return rect_fwd(ctx, gp_stat_law<F()>(sigma, l), x1, n1, x2, n2, D, K, ldk); });
 }
 
 int smg_gp_cross_cov_rev(smg_ctx* ctx, int family, const double* x1, int n1, const double* x2, int n2, int D,
                          double sigma, double l, const double* Kadj, int ldka, double* out2) {
   if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
-  if (family < SMG_GP_EXP_QUAD || family > SMG_GP_MATERN52) return SMG_ERR_ARG;
+  if (!gp_family_ok(family)) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!x1 || !x2 || !Kadj || !out2 || ldka < n1) return SMG_ERR_ARG;
-  switch (family) {
-    case SMG_GP_EXPONENTIAL:
-      return gp_cross_rev<SMG_GP_EXPONENTIAL>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
-    case SMG_GP_MATERN32: return gp_cross_rev<SMG_GP_MATERN32>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
-    case SMG_GP_MATERN52: return gp_cross_rev<SMG_GP_MATERN52>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
-    default: return gp_cross_rev<SMG_GP_EXP_QUAD>(ctx, x1, n1, x2, n2, D, sigma, l, Kadj, ldka, out2);
-  }
+  return gp_with_family(family, [&](auto F) {
+    return rect_rev(ctx, gp_stat_law<F()>(sigma, l), x1, n1, x2, n2, D, Kadj, ldka, out2);
+  });
 }
 
 int smg_gp_exp_quad_cov_tangent_fwd(smg_ctx* ctx, const double* x, int n, double sigma, double l,
@@ -960,325 +1052,12 @@ int smg_add_diag_rev(smg_ctx* ctx, const double* Ba, int ldb, int n, double* Aa,
   return SMG_OK;
 }
 
-}  // extern "C"
-
-// gp_periodic_cov and gp_dot_prod_cov (Stan Math 3.0.0, prim/mat/fun/), square
-// and cross: rectangular entries, the square K(x, x) being x1 == x2.  The
-// kernels keep the cross kernels' shape (a workgroup walks whole columns j,
-// x2_j in a register for D == 1 and staged in LDS otherwise, lanes on
-// consecutive rows, the 16-byte form where col2_ok allows, blockIdx.y over the
-// rows by cross_grid) and their reductions (per-workgroup partials in
-// SMG_WS_RED, one ordered pass, no atomics).
-//
-// Periodic, a = pi d / p:  K = s2 exp(-2 sin^2(a) / l^2),
-//   dK/dsigma = 2 K / sigma,  dK/dl = K 4 sin^2(a) / l^3,
-//   dK/dp = K (2 pi d / (l^2 p^2)) sin(2a).
-// sin(a) and cos(a) come from one sincospi(d / p) (the forward needs sinpi
-// alone), d / p as d times the host's 1 / p: exact argument reduction, so a
-// pair a whole number of periods apart gives s2 when d / p is exact, and
-// sin(2a) = 2 sin cos.  Every position alike, no diagonal: d = 0 gives s2
-// exp(-0) = s2, and the sign of the difference drops out of |.| and of the
-// squares, so x1 == x2 gives a bitwise symmetric K.
-//
-// Dot product:  K_ij = sigma^2 + sum_d x1_id x2_jd in coordinate order (the
-// product commutes, so x1 == x2 is bitwise symmetric), dK/dsigma = 2 sigma:
-// the reverse is the sum of the adjoint.
-namespace {
-
-// cn = -2 / l^2
-__device__ __forceinline__ double per_k(double d, double s2, double inv_p, double cn) {
-  const double s = sinpi(d * inv_p);
-  return s2 * exp(cn * (s * s));
-}
-// as += a K, al += a K sin^2, ap += a K d sin cos
-__device__ __forceinline__ void per_acc(double a, double d, double s2, double inv_p, double cn, double& as,
-                                        double& al, double& ap) {
-  double s, c;
-  sincospi(d * inv_p, &s, &c);
-  const double ss = s * s;
-  const double ak = a * (s2 * exp(cn * ss));
-  as += ak;
-  al += ak * ss;
-  ap += ak * (d * (s * c));
-}
-
-__global__ __launch_bounds__(256) void k_gp_per_fwd_col2(const double* __restrict__ x1, int n1,
-                                                         const double* __restrict__ x2, int n2, double s2,
-                                                         double inv_p, double cn, double* __restrict__ K, int ldk) {
-  const int np = n1 >> 1;
-  const double2* xr = reinterpret_cast<const double2*>(x1);
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          const double2 xi = xr[p];
-          double2 v;
-          v.x = per_k(fabs(xi.x - xj), s2, inv_p, cn);
-          v.y = per_k(fabs(xi.y - xj), s2, inv_p, cn);
-          col[p] = v;
-        }
-      }
-    }
-  }
-}
-
-// Generic form: any n1 and ldk (rows n1 .. ldk - 1 are not written)
-__global__ __launch_bounds__(256) void k_gp_per_fwd(const double* __restrict__ x1, int n1,
-                                                    const double* __restrict__ x2, int n2, double s2, double inv_p,
-                                                    double cn, double* __restrict__ K, int ldk) {
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double* col = K + (size_t)j * ldk;
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256)
-      col[i] = per_k(fabs(x1[i] - xj), s2, inv_p, cn);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gp_per_nd_fwd(const double* __restrict__ x1, int n1,
-                                                       const double* __restrict__ x2, int n2, int D, double s2,
-                                                       double inv_p, double cn, double* __restrict__ K, int ldk) {
-  extern __shared__ double xj[];
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    __syncthreads();
-    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
-    __syncthreads();
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
-      const double* xi = x1 + (size_t)i * D;
-      double d2 = 0.0;
-      for (int d = 0; d < D; ++d) {
-        const double t = xi[d] - xj[d];
-        d2 += t * t;
-      }
-      K[i + (size_t)j * ldk] = per_k(sqrt(d2), s2, inv_p, cn);
-    }
-  }
-}
-
-// a workgroup's three sums -> part[3 b ..]
-__device__ __forceinline__ void per_store_partials(double as, double al, double ap, double* lds,
-                                                   double* __restrict__ part) {
-  const double ss = block_sum(as, lds);
-  __syncthreads();
-  const double sl = block_sum(al, lds);
-  __syncthreads();
-  const double sp = block_sum(ap, lds);
-  if (threadIdx.x == 0) {
-    const int b = blockIdx.y * gridDim.x + blockIdx.x;
-    part[3 * b + 0] = ss;
-    part[3 * b + 1] = sl;
-    part[3 * b + 2] = sp;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gp_per_rev_partials_col2(const double* __restrict__ x1, int n1,
-                                                                  const double* __restrict__ x2, int n2, double s2,
-                                                                  double inv_p, double cn,
-                                                                  const double* __restrict__ Ka, int lda,
-                                                                  double* __restrict__ part) {
-  __shared__ double lds[16];
-  const int np = n1 >> 1;
-  const double2* xr = reinterpret_cast<const double2*>(x1);
-  double as = 0.0, al = 0.0, ap = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-      double2 a[4], xi[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          a[k] = col[p];
-          xi[k] = xr[p];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          per_acc(a[k].x, fabs(xi[k].x - xj), s2, inv_p, cn, as, al, ap);
-          per_acc(a[k].y, fabs(xi[k].y - xj), s2, inv_p, cn, as, al, ap);
-        }
-      }
-    }
-  }
-  per_store_partials(as, al, ap, lds, part);
-}
-
-// Generic form, D >= 1 (x2_j staged in LDS; D == 1 from the difference)
-__global__ __launch_bounds__(256) void k_gp_per_rev_partials(const double* __restrict__ x1, int n1,
-                                                             const double* __restrict__ x2, int n2, int D, double s2,
-                                                             double inv_p, double cn, const double* __restrict__ Ka,
-                                                             int lda, double* __restrict__ part) {
-  extern __shared__ double xj[];
-  __shared__ double lds[16];
-  double as = 0.0, al = 0.0, ap = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    __syncthreads();
-    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
-    __syncthreads();
-    const double* col = Ka + (size_t)j * lda;
-    const double xj0 = xj[0];
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
-      const double a = col[i];
-      if (D == 1) {
-        per_acc(a, fabs(x1[i] - xj0), s2, inv_p, cn, as, al, ap);
-      } else {
-        const double* xi = x1 + (size_t)i * D;
-        double d2 = 0.0;
-        for (int d = 0; d < D; ++d) {
-          const double t = xi[d] - xj[d];
-          d2 += t * t;
-        }
-        per_acc(a, sqrt(d2), s2, inv_p, cn, as, al, ap);
-      }
-    }
-  }
-  per_store_partials(as, al, ap, lds, part);
-}
-
-// out3 += [2 ss / sigma, 4 sl / l^3, 4 pi sp / (l^2 p^2)] (sp carries sin cos = sin(2a) / 2)
-__global__ void k_gp_per_rev_final(const double* __restrict__ part, int nparts, double sigma, double l, double p,
-                                   double* out3) {
-  __shared__ double lds[16];
-  double ss = 0.0, sl = 0.0, sp = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    ss += part[3 * i];
-    sl += part[3 * i + 1];
-    sp += part[3 * i + 2];
-  }
-  ss = block_sum(ss, lds);
-  __syncthreads();
-  sl = block_sum(sl, lds);
-  __syncthreads();
-  sp = block_sum(sp, lds);
-  if (threadIdx.x == 0) {
-    out3[0] += ss * 2 / sigma;
-    out3[1] += 4 * sl / (l * l * l);
-    out3[2] += 4 * 3.14159265358979323846 * sp / (l * l * p * p);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gp_dot_fwd_col2(const double* __restrict__ x1, int n1,
-                                                         const double* __restrict__ x2, int n2, double s2,
-                                                         double* __restrict__ K, int ldk) {
-  const int np = n1 >> 1;
-  const double2* xr = reinterpret_cast<const double2*>(x1);
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double2* col = reinterpret_cast<double2*>(K + (size_t)j * ldk);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        if (p < np) {
-          const double2 xi = xr[p];
-          double2 v;
-          v.x = s2 + xi.x * xj;
-          v.y = s2 + xi.y * xj;
-          col[p] = v;
-        }
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gp_dot_fwd(const double* __restrict__ x1, int n1,
-                                                    const double* __restrict__ x2, int n2, double s2,
-                                                    double* __restrict__ K, int ldk) {
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double xj = x2[j];
-    double* col = K + (size_t)j * ldk;
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) col[i] = s2 + x1[i] * xj;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gp_dot_nd_fwd(const double* __restrict__ x1, int n1,
-                                                       const double* __restrict__ x2, int n2, int D, double s2,
-                                                       double* __restrict__ K, int ldk) {
-  extern __shared__ double xj[];
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    __syncthreads();
-    for (int d = threadIdx.x; d < D; d += blockDim.x) xj[d] = x2[(size_t)j * D + d];
-    __syncthreads();
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) {
-      const double* xi = x1 + (size_t)i * D;
-      double dot = 0.0;
-      for (int d = 0; d < D; ++d) dot += xi[d] * xj[d];
-      K[i + (size_t)j * ldk] = s2 + dot;
-    }
-  }
-}
-
-// The dot product's reverse: per-workgroup sums of the n1 x n2 adjoint over the same walks
-__global__ __launch_bounds__(256) void k_gp_dot_rev_partials_col2(int n1, int n2, const double* __restrict__ Ka,
-                                                                  int lda, double* __restrict__ part) {
-  __shared__ double lds[16];
-  const int np = n1 >> 1;
-  double as = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double2* col = reinterpret_cast<const double2*>(Ka + (size_t)j * lda);
-    for (int p0 = blockIdx.y * (4 * 256) + threadIdx.x; p0 < np; p0 += gridDim.y * (4 * 256)) {
-      double2 a[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int p = p0 + 256 * k;
-        a[k] = p < np ? col[p] : make_double2(0.0, 0.0);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) as += a[k].x + a[k].y;
-    }
-  }
-  const double s = block_sum(as, lds);
-  if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(256) void k_gp_dot_rev_partials(int n1, int n2, const double* __restrict__ Ka, int lda,
-                                                             double* __restrict__ part) {
-  __shared__ double lds[16];
-  double as = 0.0;
-  for (int j = blockIdx.x; j < n2; j += gridDim.x) {
-    const double* col = Ka + (size_t)j * lda;
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n1; i += gridDim.y * 256) as += col[i];
-  }
-  const double s = block_sum(as, lds);
-  if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = s;
-}
-
-__global__ void k_gp_dot_rev_final(const double* __restrict__ part, int nparts, double sigma, double* out1) {
-  __shared__ double lds[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += part[i];
-  s = block_sum(s, lds);
-  if (threadIdx.x == 0) out1[0] += 2 * sigma * s;
-}
-
-}  // namespace
-
-extern "C" {
-
 int smg_gp_periodic_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
                             double l, double p, double* K, int ldk) {
   if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma, inv_p = 1.0 / p, cn = -2.0 / (l * l);
-  if (D > 1)
-    hipLaunchKernelGGL(k_gp_per_nd_fwd, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2,
-                       n2, D, s2, inv_p, cn, K, ldk);
-  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
-    hipLaunchKernelGGL(k_gp_per_fwd_col2, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2,
-                       inv_p, cn, K, ldk);
-  else
-    hipLaunchKernelGGL(k_gp_per_fwd, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, inv_p, cn,
-                       K, ldk);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return rect_fwd(ctx, gp_per_law(sigma, l, p), x1, n1, x2, n2, D, K, ldk);
 }
 
 int smg_gp_periodic_cov_rev(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
@@ -1286,22 +1065,7 @@ int smg_gp_periodic_cov_rev(smg_ctx* ctx, const double* x1, int n1, const double
   if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!x1 || !x2 || !Kadj || !out3 || ldka < n1) return SMG_ERR_ARG;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma, inv_p = 1.0 / p, cn = -2.0 / (l * l);
-  const bool col2 = D == 1 && col2_ok(x1, 2, n1) && col2_ok(Kadj, ldka, n1);
-  const dim3 grid = cross_grid(n1, n2, col2 ? 8 * 256 : 256);
-  const int nb = (int)(grid.x * grid.y);
-  double* part = smg_ws(ctx, SMG_WS_RED, 3 * (size_t)nb);
-  if (!part) return SMG_ERR_OOM;
-  if (col2)
-    hipLaunchKernelGGL(k_gp_per_rev_partials_col2, grid, dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, inv_p, cn, Kadj,
-                       ldka, part);
-  else
-    hipLaunchKernelGGL(k_gp_per_rev_partials, grid, dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2, n2, D, s2,
-                       inv_p, cn, Kadj, ldka, part);
-  hipLaunchKernelGGL(k_gp_per_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, l, p, out3);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return rect_rev(ctx, gp_per_law(sigma, l, p), x1, n1, x2, n2, D, Kadj, ldka, out3);
 }
 
 int smg_gp_dot_prod_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double* x2, int n2, int D, double sigma,
@@ -1309,20 +1073,10 @@ int smg_gp_dot_prod_cov_fwd(smg_ctx* ctx, const double* x1, int n1, const double
   if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > 8192) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!x1 || !x2 || !K || ldk < n1) return SMG_ERR_ARG;
-  smg_prof_scope prof(ctx, SMG_FAM_GP);
-  const double s2 = sigma * sigma;
-  if (D > 1)
-    hipLaunchKernelGGL(k_gp_dot_nd_fwd, cross_grid(n1, n2, 256), dim3(256), D * sizeof(double), ctx->stream, x1, n1, x2,
-                       n2, D, s2, K, ldk);
-  else if (col2_ok(x1, 2, n1) && col2_ok(K, ldk, n1))
-    hipLaunchKernelGGL(k_gp_dot_fwd_col2, cross_grid(n1, n2, 8 * 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, K,
-                       ldk);
-  else
-    hipLaunchKernelGGL(k_gp_dot_fwd, cross_grid(n1, n2, 256), dim3(256), 0, ctx->stream, x1, n1, x2, n2, s2, K, ldk);
-  SMG_LAUNCH_CHECK();
-  return SMG_OK;
+  return rect_fwd(ctx, gp_dot_law(sigma), x1, n1, x2, n2, D, K, ldk);
 }
 
+// (no points to read: its own two partials kernels, the walk's grid and final pass)
 int smg_gp_dot_prod_cov_rev(smg_ctx* ctx, int n1, int n2, double sigma, const double* Kadj, int ldka, double* out1) {
   if (!ctx || n1 < 0 || n2 < 0) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
@@ -1337,7 +1091,7 @@ int smg_gp_dot_prod_cov_rev(smg_ctx* ctx, int n1, int n2, double sigma, const do
     hipLaunchKernelGGL(k_gp_dot_rev_partials_col2, grid, dim3(256), 0, ctx->stream, n1, n2, Kadj, ldka, part);
   else
     hipLaunchKernelGGL(k_gp_dot_rev_partials, grid, dim3(256), 0, ctx->stream, n1, n2, Kadj, ldka, part);
-  hipLaunchKernelGGL(k_gp_dot_rev_final, dim3(1), dim3(1024), 0, ctx->stream, part, nb, sigma, out1);
+  hipLaunchKernelGGL(k_gp_rect_final<gp_dot_law>, dim3(1), dim3(1024), 0, ctx->stream, gp_dot_law(sigma), part, nb, out1);
   SMG_LAUNCH_CHECK();
   return SMG_OK;
 }

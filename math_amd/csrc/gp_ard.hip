@@ -225,8 +225,6 @@ inline ard_scales host_scales(const double* l, int D) {
   return r;
 }
 
-inline bool family_ok(int family) { return family >= SMG_GP_EXP_QUAD && family <= SMG_GP_MATERN52; }
-
 template <int F, int DP>
 void launch_rev(smg_ctx* ctx, int nb, const double* zt, int D, int n, double s2, const double* Ka, int lda,
                 double* part) {
@@ -287,15 +285,7 @@ void launch_cross_rev(smg_ctx* ctx, dim3 grid, const double* z1t, int n1, const 
     else if (D <= 8) FN<F, 8>(__VA_ARGS__);        \
     else FN<F, ARD_PASS>(__VA_ARGS__);             \
   } while (0)
-#define ARD_DISPATCH(FN, ...)                                                      \
-  do {                                                                             \
-    switch (family) {                                                              \
-      case SMG_GP_EXPONENTIAL: ARD_DISPATCH_DP(FN, SMG_GP_EXPONENTIAL, __VA_ARGS__); break; \
-      case SMG_GP_MATERN32: ARD_DISPATCH_DP(FN, SMG_GP_MATERN32, __VA_ARGS__); break;       \
-      case SMG_GP_MATERN52: ARD_DISPATCH_DP(FN, SMG_GP_MATERN52, __VA_ARGS__); break;       \
-      default: ARD_DISPATCH_DP(FN, SMG_GP_EXP_QUAD, __VA_ARGS__); break;                    \
-    }                                                                              \
-  } while (0)
+#define ARD_DISPATCH(FN, ...) gp_with_family(family, [&](auto F) { ARD_DISPATCH_DP(FN, F(), __VA_ARGS__); })
 
 }  // namespace
 
@@ -316,7 +306,7 @@ int smg_gp_ard_scale(smg_ctx* ctx, const double* x, int D, int n, const double* 
 
 int smg_gp_ard_cov_rev(smg_ctx* ctx, int family, const double* zt, int D, int n, double sigma, const double* l,
                        const double* Kadj, int ldka, double* out) {
-  if (!ctx || n < 0 || D < 1 || D > SMG_GP_ARD_MAX_D || !family_ok(family)) return SMG_ERR_ARG;
+  if (!ctx || n < 0 || D < 1 || D > SMG_GP_ARD_MAX_D || !gp_family_ok(family)) return SMG_ERR_ARG;
   if (n > 0 && (!zt || !l || !Kadj || !out || ldka < n)) return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
   smg_prof_scope prof(ctx, SMG_FAM_GP);
@@ -332,16 +322,12 @@ int smg_gp_ard_cov_rev(smg_ctx* ctx, int family, const double* zt, int D, int n,
 
 int smg_gp_ard_cross_cov_rev(smg_ctx* ctx, int family, const double* z1t, int n1, const double* z2t, int n2, int D,
                              double sigma, const double* l, const double* Kadj, int ldka, double* out) {
-  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > SMG_GP_ARD_MAX_D || !family_ok(family)) return SMG_ERR_ARG;
+  if (!ctx || n1 < 0 || n2 < 0 || D < 1 || D > SMG_GP_ARD_MAX_D || !gp_family_ok(family)) return SMG_ERR_ARG;
   if (n1 == 0 || n2 == 0) return SMG_OK;
   if (!z1t || !z2t || !l || !Kadj || !out || ldka < n1) return SMG_ERR_ARG;
   smg_prof_scope prof(ctx, SMG_FAM_GP);
-  // one workgroup per column, times row parts up to about 2048 workgroups (gp.hip's cross_grid)
-  const int gx = n2 < 2048 ? n2 : 2048;
-  int gy = (n1 + 255) / 256;
-  if (gy > 2048 / gx) gy = 2048 / gx;
-  const dim3 grid(gx, gy);
-  const int nb = gx * gy;
+  const dim3 grid = cross_grid(n1, n2, 256);
+  const int nb = (int)(grid.x * grid.y);
   double* part = smg_ws(ctx, SMG_WS_RED, (size_t)(D + 2) * nb);
   if (!part) return SMG_ERR_OOM;
   ARD_DISPATCH(launch_cross_rev, ctx, grid, z1t, n1, z2t, n2, D, sigma * sigma, Kadj, ldka, part);
@@ -354,7 +340,7 @@ int smg_gp_ard_cross_cov_rev(smg_ctx* ctx, int family, const double* z1t, int n1
 int smg_gp_ard_cov_inverse_adjoint(smg_ctx* ctx, int family, const double* C, int ldc, int n, const double* s, int k,
                                    long long s_stride, double adj, const double* zt, int D, double sigma,
                                    const double* l, double* dadj, double* out) {
-  if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1 || D > SMG_GP_ARD_MAX_D || !family_ok(family))
+  if (!ctx || n < 0 || k < 1 || (k > 1 && s_stride < n) || D < 1 || D > SMG_GP_ARD_MAX_D || !gp_family_ok(family))
     return SMG_ERR_ARG;
   if (n == 0) return SMG_OK;
   if (!C || !s || ldc < n || (out && (!zt || !l || !(sigma > 0)))) return SMG_ERR_ARG;

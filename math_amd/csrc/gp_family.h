@@ -24,11 +24,38 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "smg_hip.h"
 
 template <int F>
 struct gp_fam;
+
+inline bool gp_family_ok(int family) { return family >= SMG_GP_EXP_QUAD && family <= SMG_GP_MATERN52; }
+
+// fn(F) with the family as a compile-time constant (gp_fam<F()>); exp_quad for any other value
+template <class Fn>
+auto gp_with_family(int family, Fn&& fn) {
+  switch (family) {
+    case SMG_GP_EXPONENTIAL: return fn(std::integral_constant<int, SMG_GP_EXPONENTIAL>());
+    case SMG_GP_MATERN32: return fn(std::integral_constant<int, SMG_GP_MATERN32>());
+    case SMG_GP_MATERN52: return fn(std::integral_constant<int, SMG_GP_MATERN52>());
+    default: return fn(std::integral_constant<int, SMG_GP_EXP_QUAD>());
+  }
+}
+
+// The grid of the rectangular walks over an n1 x n2 K (gp.hip's k_gp_rect_*,
+// gp_ard.hip's cross reverse): one workgroup per column up to GP_BLOCKS (the
+// column loop wraps beyond), times as many row parts as bring the grid to about
+// GP_BLOCKS workgroups, none of them without rows; rows: what a workgroup
+// covers in one pass.
+constexpr int GP_BLOCKS = 2048;
+inline dim3 cross_grid(int n1, int n2, int rows) {
+  const int gx = n2 < GP_BLOCKS ? n2 : GP_BLOCKS;
+  int gy = (int)(((long long)n1 + rows - 1) / rows);
+  if (gy > GP_BLOCKS / gx) gy = GP_BLOCKS / gx;
+  return dim3(gx, gy < 1 ? 1 : gy);
+}
 
 template <>
 struct gp_fam<SMG_GP_EXP_QUAD> {

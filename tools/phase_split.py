@@ -14,7 +14,7 @@ starts = [i for i, n in enumerate(names) if n.startswith("k_gp_fwd")]
 i0 = starts[-1]
 t0 = rows[i0][2]
 mark = ("k_gp_fwd", "k_add_diag_fwd", "k_check_symmetric", "k_chol_panel", "k_inv_double_diag", "k_trsv_persist",
-        "k_mvn_rev", "k_tril_copy", "k_half_lower", "k_add_lower", "k_gp_rev_partials", "k_gp_rev_final")
+        "k_mvn_rev", "k_tril_copy", "k_half_lower", "k_add_lower", "k_gp_rev_partials", "k_gp_rect_final")
 for i in range(i0, len(rows)):
     n = names[i]
     if n.startswith(mark):
