@@ -17,7 +17,7 @@
 // when it can prove no other node wrote the factor's adjoint
 // (stan/math/rev/fun/cholesky_decompose.hpp).
 #include "smg_internal.h"
-#include "tri_small.h"
+#include "blk_sizes.h"
 #include "gp_family.h"
 
 #include <vector>

@@ -23,7 +23,7 @@
 // are the same sums.  Total ~5.3 N^3 instead of 7 N^3, in GEMMs whose K
 // ranges are cut to the triangles.
 #include "smg_internal.h"
-#include "tri_small.h"
+#include "blk_sizes.h"
 
 namespace {
 

@@ -316,7 +316,7 @@ typedef __attribute__((address_space(3))) double lds_dbl;
 // time (wave_factor8_pair2: the 2 x 2 leading minors' two roots side by side,
 // rsq_h roots, the later columns updated with the factor's own entries
 // broadcast from the lanes that form them)
-__device__ __noinline__ void chain_factor(lds_dbl* D, int* status) { lds_potrf64_v3<3, false>(D, status); }
+__device__ __noinline__ void chain_factor(lds_dbl* D, int* status) { lds_potrf64_chain(D, status); }
 // the chain's leaves also stored (sc1) into the diagonal 16 x 16 blocks of
 // Dinv_j (G = Dinv + cj, ld ldg; the inverter later writes the same bits
 // there), published with diag[j]: the panel tiles load them instead of

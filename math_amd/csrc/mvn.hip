@@ -15,7 +15,7 @@
 #include <cmath>
 
 #include "smg_internal.h"
-#include "tri_small.h"
+#include "blk_sizes.h"
 
 namespace {
 

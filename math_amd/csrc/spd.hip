@@ -21,7 +21,6 @@
 //     (prim/mat/fun/quad_form_sym.hpp:11-18) and autodiffs 0.5 (Cd + Cd^T):
 //     sym_adj = 1 replaces Cadj by sym(Cadj) = (Cadj + Cadj^T)/2
 #include "smg_internal.h"
-#include "tri_small.h"
 
 namespace {
 

@@ -15,7 +15,7 @@
 // the 64-row level.
 #include "smg_internal.h"
 #include "smg_sync.h"
-#include "tri_small.h"
+#include "blk_sizes.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // Dev microbenchmark: the phases of the panel chain's 64x64 step in one
-// 512-thread workgroup (lds_potrf64_lookahead, lds_trtri64_mfma, the two 64^3
+// 512-thread workgroup (lds_potrf64_chain, lds_trtri64_mfma, the two 64^3
 // LDS products), timed with s_memrealtime (100 MHz) inside the kernel.
 #include <hip/hip_runtime.h>
 
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(512) void k_chain_phases(const double* g, unsigned 
     lds_load_block(Y, g, 64, 64, false);
     __syncthreads();
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    lds_potrf64_lookahead(D, st);
+    lds_potrf64_chain(D, st);
     __syncthreads();
     const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
     lds_trtri64_mfma(D, X, T);

@@ -1,14 +1,16 @@
-// Dev microbenchmark (round 6): the chain's 64 x 64 factor variants
-// (lds_potrf64_v3<PANEL, AMFMA>, tri_small.h) against the library's
-// lds_potrf64_lookahead<true>: cycles (s_memtime, 2.4 GHz) and accuracy
-// against a long-double Cholesky, on a well-conditioned block and on a GP
-// kernel block (close points, small jitter).
+// Dev microbenchmark (round 6): the library's chain factor
+// (lds_potrf64_chain, tri_small.h: what chain_factor in cholesky.hip calls)
+// against the variants that were measured and dropped
+// (lds_potrf64_v3<PANEL, AMFMA>, ubench_variants.h; <0, false> is the round-5
+// library factor): cycles (s_memtime, 2.4 GHz) and accuracy against a
+// long-double Cholesky, on a well-conditioned block and on a GP kernel block
+// (close points, small jitter).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <cmath>
 #include <algorithm>
-#include "../math_amd/csrc/tri_small.h"
+#include "ubench_variants.h"
 
 typedef __attribute__((address_space(3))) double lds_dbl;
 __device__ __forceinline__ long long stamp() {
@@ -19,13 +21,13 @@ __device__ __forceinline__ long long stamp() {
   return t;
 }
 template <int V> __device__ __noinline__ void fac(lds_dbl* D, int* st) {
-  if (V == 0) lds_potrf64_lookahead<true>(D, st);
+  if (V == 0) lds_potrf64_chain(D, st);
   if (V == 1) lds_potrf64_v3<1, false>(D, st);
   if (V == 2) lds_potrf64_v3<2, false>(D, st);
   if (V == 3) lds_potrf64_v3<0, true>(D, st);
   if (V == 4) lds_potrf64_v3<1, true>(D, st);
   if (V == 5) lds_potrf64_v3<2, true>(D, st);
-  if (V == 6) lds_potrf64_v3<3, false>(D, st);
+  if (V == 6) lds_potrf64_v3<0, false>(D, st);
 }
 template <int V>
 __global__ __launch_bounds__(512) void k_fac(const double* g, double* out, long long* cyc, int* st) {
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(512) void k_leaf(const double* g, double* out, long
   lds_load_block(D, g, 64, 64, true);
   for (int e = threadIdx.x; e < SMG_NB * SMG_NBP; e += blockDim.x) X[e] = 0.0;
   __syncthreads();
-  lds_potrf64_lookahead<true>((lds_dbl*)D, (int*)(cyc + 8));
+  lds_potrf64_chain((lds_dbl*)D, (int*)(cyc + 8));
   __syncthreads();
   const long long t0 = stamp();
   const int w = threadIdx.x >> 6;
@@ -60,8 +62,8 @@ __global__ __launch_bounds__(512) void k_leaf(const double* g, double* out, long
 }
 
 int main() {
-  const char* names[7] = {"lookahead pairs (lib)", "pairs + rsq_h", "uniform + rsq_h", "pairs + MFMA (A)",
-                          "pairs rsq_h + MFMA (A)", "uniform + MFMA (A)", "pair2 (own entries bcast)"};
+  const char* names[7] = {"pair2, rsq_h (lib)", "pairs + rsq_h", "uniform + rsq_h", "pairs + MFMA (A)",
+                          "pairs rsq_h + MFMA (A)", "uniform + MFMA (A)", "pairs, Newton (round 5)"};
   void (*ks[7])(const double*, double*, long long*, int*) = {k_fac<0>, k_fac<1>, k_fac<2>, k_fac<3>, k_fac<4>, k_fac<5>, k_fac<6>};
   double *dA, *dO;
   long long* dc;

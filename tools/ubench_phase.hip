@@ -1,10 +1,12 @@
-// Dev microbenchmark: phase times (s_memtime) of lds_potrf64_lookahead's pieces.
+// Dev microbenchmark: phase times (s_memtime) of lds_potrf64_lookahead's pieces
+// (tri_small.h) and of the panel factors measured against them
+// (ubench_variants.h; "pairs" is lds_potrf64_v3<0, false>, the round-5 factor).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <cmath>
 #include <algorithm>
-#include "../math_amd/csrc/tri_small.h"
+#include "ubench_variants.h"
 
 __device__ __forceinline__ long long stamp() {
   __builtin_amdgcn_s_waitcnt(0);
@@ -16,8 +18,8 @@ __device__ __forceinline__ long long stamp() {
 
 typedef __attribute__((address_space(3))) double lds_dbl;
 // the panel kernel's form: out of line, address_space(3) pointers
-__device__ __noinline__ void cf_pair(lds_dbl* D, int* st) { lds_potrf64_lookahead<true>(D, st); }
-__device__ __noinline__ void cf_old(lds_dbl* D, int* st) { lds_potrf64_lookahead<false>(D, st); }
+__device__ __noinline__ void cf_pair(lds_dbl* D, int* st) { lds_potrf64_v3<0, false>(D, st); }
+__device__ __noinline__ void cf_old(lds_dbl* D, int* st) { lds_potrf64_lookahead(D, st); }
 
 template <int WHICH>
 __global__ __launch_bounds__(512) void k_phase(double* g, long long* cyc) {
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(512) void k_phase(double* g, long long* cyc) {
   if (WHICH == 9) cf_old((lds_dbl*)D, (int*)(cyc + 60));
   if (WHICH == 2) lds_potrf64_lookahead(D, (int*)(cyc + 60));
   if (WHICH == 3) lds_potrf64_lookahead(D, (int*)(cyc + 60));
-  if (WHICH == 7) lds_potrf64_lookahead<true>(D, (int*)(cyc + 60));
+  if (WHICH == 7) lds_potrf64_v3<0, false>(D, (int*)(cyc + 60));
   if (WHICH == 4 || WHICH == 5) {
     __shared__ double X[SMG_NB * SMG_NBP];
     __shared__ double T[768];
